@@ -7,6 +7,9 @@ Multi GPU:    python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
                   --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line with the whole-job aggregate throughput.
+A plain run sets up, warms up, times exactly --steps steps and prints that
+line; --dump-outputs DIR also saves the last step's results as .npy, and
+--full is where any measurement beyond the headline figure goes.
 """
 
 import argparse
@@ -50,7 +53,69 @@ def parse_args():
     p.add_argument("--allow-cpu", action="store_true")
     p.add_argument("--lr", type=float, default=0.01)
     p.add_argument("--momentum", type=float, default=0.9)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed "
+                        "step produced (its loss, and a fixed seeded sample "
+                        "of the parameters it updated) as DIR/<name>.npy, "
+                        "float32. That step then starts from the seeded "
+                        "initial state, so the files depend on the "
+                        "arguments alone")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline "
+                        "figure. The flagship benchmark has none today "
+                        "(per-shape and profiling runs live in tools/), so "
+                        "this adds nothing yet; new extras belong behind it")
     return p.parse_args()
+
+
+# dump at most this many elements per sampled array (4 MB of float32 each)
+_DUMP_SAMPLE = 1 << 20
+
+
+def _training_state(model, opt):
+    """Every tensor a train step reads and updates in place: the flat
+    parameter buffers, their fp32 masters, the momentum, the BN buffers."""
+    ts = [t for g in opt.groups for t in (g.P, g.master, g.V) if t is not None]
+    return ts + [b for b in model.buffers() if b.is_floating_point()]
+
+
+def _snapshot(tensors):
+    return [(t, t.detach().clone()) for t in tensors]
+
+
+@torch.no_grad()
+def _restore(snapshot):
+    from fluxdistributed_amd.ops.conv import bump_conv_wt_marker
+
+    for t, saved in snapshot:
+        t.copy_(saved)
+    bump_conv_wt_marker()  # cached transposed weights are stale now
+
+
+def _dump_outputs(dirname, loss, opt):
+    """Write the last timed step's results for build-to-build comparison:
+    the loss the step returned, and the parameters it left updated (the
+    fp32 master copy where the model computes in bf16), reduced to a fixed
+    seeded sample of _DUMP_SAMPLE elements so the file stays a few MB.
+
+    With --dump-outputs the last timed step starts from the seeded initial
+    state (main() restores it), so these are a function of the arguments
+    alone. Without that they are not: the weight-gradient kernels
+    accumulate with atomics, and training from random initialisation
+    amplifies that rounding noise until, after ~10 steps, two runs of the
+    SAME build differ by far more than rounding (docs/benchmarking.md)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "loss.npy"),
+            loss.detach().float().cpu().numpy().reshape(1))
+    t = torch.cat([(g.master if g.master is not None else g.P).detach().float()
+                   for g in opt.groups])
+    if t.numel() > _DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(2024)
+        idx = torch.randint(0, t.numel(), (_DUMP_SAMPLE,), generator=g)
+        t = t[idx.sort().values.to(t.device)]
+    np.save(os.path.join(dirname, "params.npy"), t.cpu().numpy())
 
 
 def _miopen_env():
@@ -101,6 +166,9 @@ def main():
     dist = torch.distributed if world > 1 else None
 
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
+    # same initial weights on every run and rank (the batches are seeded
+    # below), so two builds can be compared output for output
+    torch.manual_seed(1234)
     model = build_model(args.model, num_classes=args.num_classes)
     model = model.to(device).to(memory_format=torch.channels_last)
     if dtype == torch.bfloat16:
@@ -112,6 +180,11 @@ def main():
     if world > 1:
         ddp = DDPModel(model, opt, bucket_cap_mb=args.bucket_mb,
                        overlap=not args.no_overlap)
+
+    # --dump-outputs: keep the seeded initial state, to put it back before
+    # the last timed step (see _dump_outputs). A plain run does neither.
+    initial = (_snapshot(_training_state(model, opt))
+               if args.dump_outputs else None)
 
     batcher = SyntheticBatcher(
         args.batch, num_classes=args.num_classes, size=args.image_size,
@@ -145,7 +218,9 @@ def main():
 
     # ---- timed region: exactly --steps steps ----
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if initial is not None and i == args.steps - 1:
+            _restore(initial)  # device-side copies, once
         loss = step()
     if device.type == "cuda":
         torch.cuda.synchronize(device)
@@ -164,6 +239,9 @@ def main():
     total_images = args.steps * args.batch * max(world, 1)
     images_per_sec = total_images / elapsed
     ms_per_step = elapsed / args.steps * 1e3
+
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, loss, opt)
 
     if rank == 0:
         print(json.dumps({

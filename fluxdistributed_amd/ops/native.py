@@ -5,11 +5,12 @@ built in-tree so the .so travels with the repo snapshot to GPU machines.
 """
 
 import os
-
+import threading
 
 
 _NATIVE = None
 _TRIED = False
+_LOCK = threading.Lock()
 
 
 def load_native():
@@ -17,13 +18,20 @@ def load_native():
     global _NATIVE, _TRIED
     if _TRIED:
         return _NATIVE
-    _TRIED = True
-    try:
-        from fluxdistributed_amd import _C  # noqa: F401  (in-tree .so)
+    # Replica threads (parallel/task_ddp.py) can get here together on the
+    # first step. _TRIED is set only once the import has finished, under the
+    # lock: a thread arriving while another is still loading the .so (slow
+    # when the file is cold) must wait for it, not see "tried, and absent".
+    with _LOCK:
+        if _TRIED:
+            return _NATIVE
+        try:
+            from fluxdistributed_amd import _C  # noqa: F401  (in-tree .so)
 
-        _NATIVE = _C
-    except ImportError:
-        _NATIVE = None
+            _NATIVE = _C
+        except ImportError:
+            _NATIVE = None
+        _TRIED = True
     return _NATIVE
 
 

@@ -43,7 +43,11 @@ def test_train_cli_process_mode_world2(tmp_path):
            "--num-classes", "8", "--dtype", "fp32", "--data", "synthetic",
            "--checkpoint-dir", str(ckdir), "--log-every", "1",
            "--val-every", "0"]
-    r = subprocess.run(cmd, cwd=root, capture_output=True, text=True,
+    # The gloo/CPU contract on every machine: with GPUs visible, process
+    # mode pins rank r to cuda:r over RCCL, which a one-GPU box cannot
+    # give two ranks. An out-of-range ordinal leaves HIP with no devices.
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
+    r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-2000:])
     assert (ckdir / "resnet18_final.pt").exists(), \
