@@ -76,25 +76,24 @@ at::Tensor add_relu_bwd(at::Tensor gout, at::Tensor out) {
     return gx;
 }
 
-std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_act_fwd(
-    at::Tensor x, at::Tensor weight, at::Tensor bias, at::Tensor running_mean,
-    at::Tensor running_var, bool training, double momentum, double eps,
-    bool relu, at::Tensor residual, c10::optional<at::Tensor> conv_part) {
+// Forward statistics -> scale/shift in ws[2C..4C), save_mean, save_invstd
+// (and the running-stat update): from the producing conv's epilogue
+// partials, BN's own stats pass, or (eval) the running stats. Shared by
+// bn_act_fwd and the fused BN+ReLU+pool forward.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_fwd_finalize(
+    const at::Tensor& x, const at::Tensor& weight, const at::Tensor& bias,
+    at::Tensor& running_mean, at::Tensor& running_var, bool training,
+    double momentum, double eps, const c10::optional<at::Tensor>& conv_part) {
     auto [rows, C] = nhwc_rows(x);
     const int V = dt_of(x) == DT::BF16 ? 8 : 4;
     TORCH_CHECK(C % V == 0, "C must be divisible by ", V);
     TORCH_CHECK((C / V) >= 256 ? (C / V) % 256 == 0 : 256 % (C / V) == 0,
                 "unsupported channel count ", C);
     TORCH_CHECK(weight.scalar_type() == at::kFloat, "BN params must be fp32");
-    const bool has_res = residual.defined() && residual.numel() > 0;
-    at::Tensor resc;
-    if (has_res) resc = residual.contiguous(at::MemoryFormat::ChannelsLast);
-
     auto fopts = x.options().dtype(at::kFloat);
     auto ws = at::empty({4 * C}, fopts);
     auto save_mean = at::empty({C}, fopts);
     auto save_invstd = at::empty({C}, fopts);
-    auto out = at::empty_like(x);
     auto stream = cur_stream();
 
     if (training && conv_part.has_value()) {
@@ -106,8 +105,9 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_act_fwd(
         at::Tensor p2;
         if (NB > 1024) {
             // layer-1-sized partial sets (~4700 m-tiles) fold at full
-            // grid width first; finalize then reads <=512 rows
-            const int NB2 = 512;
+            // grid width first; finalize then reads 256 rows, all of its
+            // loads in flight at once
+            const int NB2 = 256;
             p2 = at::empty({NB2, 2, C}, fopts);
             fda::bn_partial_prefold_launch(pp, p2.data_ptr<float>(), NB,
                                            NB2, (int)C, stream);
@@ -141,6 +141,22 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_act_fwd(
                                 save_invstd.data_ptr<float>(), rows, (int)C,
                                 training, (float)momentum, (float)eps, stream);
     }
+    return {ws, save_mean, save_invstd};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_act_fwd(
+    at::Tensor x, at::Tensor weight, at::Tensor bias, at::Tensor running_mean,
+    at::Tensor running_var, bool training, double momentum, double eps,
+    bool relu, at::Tensor residual, c10::optional<at::Tensor> conv_part) {
+    auto [rows, C] = nhwc_rows(x);
+    const bool has_res = residual.defined() && residual.numel() > 0;
+    at::Tensor resc;
+    if (has_res) resc = residual.contiguous(at::MemoryFormat::ChannelsLast);
+    auto [ws, save_mean, save_invstd] =
+        bn_fwd_finalize(x, weight, bias, running_mean, running_var, training,
+                        momentum, eps, conv_part);
+    auto out = at::empty_like(x);
+    auto stream = cur_stream();
     fda::bn_apply_launch(x.data_ptr(), has_res ? resc.data_ptr() : nullptr,
                          out.data_ptr(), ws.data_ptr<float>(), rows, (int)C,
                          relu, dt_of(x), stream);
@@ -151,8 +167,10 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_act_bwd(
     at::Tensor gout, at::Tensor x, at::Tensor weight, at::Tensor save_mean,
     at::Tensor save_invstd, at::Tensor out, bool relu, bool training,
     c10::optional<at::Tensor> gw_out, c10::optional<at::Tensor> gb_out,
-    bool want_gres) {
-    // gw_out/gb_out set: fp32 flat-G slices, written += (direct grad)
+    bool want_gres, c10::optional<at::Tensor> bias) {
+    // gw_out/gb_out set: fp32 flat-G slices, written += (direct grad).
+    // bias set on a non-residual ReLU BN: both kernels recompute the ReLU
+    // mask from x (the forward's own expression) and never read `out`.
     auto [rows, C] = nhwc_rows(x);
     auto gc = gout.contiguous(at::MemoryFormat::ChannelsLast);
     auto fopts = x.options().dtype(at::kFloat);
@@ -164,6 +182,13 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_act_bwd(
     auto stream = cur_stream();
 
     TORCH_CHECK(C % 64 == 0, "BN bwd needs C % 64 == 0, got ", C);
+    const bool xmask = relu && !want_gres && bias.has_value();
+    if (xmask)
+        TORCH_CHECK(bias->scalar_type() == at::kFloat && bias->numel() == C &&
+                    weight.scalar_type() == at::kFloat,
+                    "BN params must be fp32 [C]");
+    const float* mask_w = xmask ? weight.data_ptr<float>() : nullptr;
+    const float* mask_b = xmask ? bias->data_ptr<float>() : nullptr;
     auto part = at::empty({fda::bn_stats_partial_floats((int)C, rows, dt_of(x))},
                           fopts);
     fda::bn_bwd_stats_launch(gc.data_ptr(), x.data_ptr(), out.data_ptr(),
@@ -171,7 +196,8 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_act_bwd(
                              save_invstd.data_ptr<float>(), ws.data_ptr<float>(),
                              part.data_ptr<float>(), gw.data_ptr<float>(),
                              gb.data_ptr<float>(), rows, (int)C, relu,
-                             training, direct, dt_of(x), stream);
+                             training, direct, dt_of(x), stream, mask_w,
+                             mask_b);
     at::Tensor gres;
     if (want_gres) gres = at::empty_like(x);
     fda::bn_bwd_apply_launch(gc.data_ptr(), x.data_ptr(), out.data_ptr(),
@@ -180,8 +206,102 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_act_bwd(
                              weight.data_ptr<float>(), ws.data_ptr<float>(),
                              gx.data_ptr(),
                              want_gres ? gres.data_ptr() : nullptr,
-                             rows, (int)C, relu, training, dt_of(x), stream);
+                             rows, (int)C, relu, training, dt_of(x), stream,
+                             mask_b);
     return {gx, gw, gb, gres};
+}
+
+// ---- fused stem tail: BN + ReLU + max-pool (pool.hip) ---------------------
+
+bool bn_act_pool_supported(int64_t C, bool bf16, int64_t KH, int64_t KW,
+                           int64_t S, int64_t P) {
+    const int64_t V = bf16 ? 8 : 4;
+    if (C % 64 != 0) return false;             // finalize kernels
+    const int64_t CV = C / V;
+    if (CV > 256 || 256 % CV != 0) return false;  // fixed channels per thread
+    // argmax byte; every window must hold at least one real pixel; the
+    // backward gather handles at most 2 x 2 windows covering a pixel
+    return KH >= 1 && KW >= 1 && KH * KW <= 255 && S >= 1 && P >= 0 &&
+           2 * P <= KH && 2 * P <= KW && (KH + S - 1) / S <= 2 &&
+           (KW + S - 1) / S <= 2;
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_act_pool_fwd(
+    at::Tensor x, at::Tensor weight, at::Tensor bias, at::Tensor running_mean,
+    at::Tensor running_var, bool training, double momentum, double eps,
+    int64_t KH, int64_t KW, int64_t S, int64_t P,
+    c10::optional<at::Tensor> conv_part) {
+    auto [rows, C] = nhwc_rows(x);
+    (void)rows;
+    TORCH_CHECK(bn_act_pool_supported(C, dt_of(x) == DT::BF16, KH, KW, S, P),
+                "bn_act_pool: unsupported C=", C, " or pool geometry");
+    const int N = (int)x.size(0), H = (int)x.size(2), W = (int)x.size(3);
+    TORCH_CHECK(H + 2 * P >= KH && W + 2 * P >= KW, "pool window > input");
+    const int HO = (int)((H + 2 * P - KH) / S + 1);
+    const int WO = (int)((W + 2 * P - KW) / S + 1);
+    auto [ws, save_mean, save_invstd] =
+        bn_fwd_finalize(x, weight, bias, running_mean, running_var, training,
+                        momentum, eps, conv_part);
+    auto out = at::empty({N, C, HO, WO},
+                         x.options().memory_format(at::MemoryFormat::ChannelsLast));
+    auto idx = at::empty({(int64_t)N * HO * WO * C},
+                         x.options().dtype(at::kByte));
+    fda::bn_relu_maxpool_fwd_launch(x.data_ptr(), ws.data_ptr<float>(),
+                                    out.data_ptr(), idx.data_ptr<uint8_t>(),
+                                    N, H, W, (int)C, HO, WO, (int)KH, (int)KW,
+                                    (int)S, (int)P, dt_of(x), cur_stream());
+    return {out, idx, save_mean, save_invstd};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_act_pool_bwd(
+    at::Tensor gout, at::Tensor x, at::Tensor weight, at::Tensor bias,
+    at::Tensor save_mean, at::Tensor save_invstd, at::Tensor idx, int64_t KH,
+    int64_t KW, int64_t S, int64_t P, bool training,
+    c10::optional<at::Tensor> gw_out, c10::optional<at::Tensor> gb_out) {
+    // gout: gradient of the POOLED output; returns gx at x's resolution.
+    // gw_out/gb_out set: fp32 flat-G slices, written += (direct grad)
+    auto [rows, C] = nhwc_rows(x);
+    TORCH_CHECK(bn_act_pool_supported(C, dt_of(x) == DT::BF16, KH, KW, S, P),
+                "bn_act_pool: unsupported C=", C, " or pool geometry");
+    TORCH_CHECK(weight.scalar_type() == at::kFloat &&
+                bias.scalar_type() == at::kFloat && bias.numel() == C,
+                "BN params must be fp32 [C]");
+    const int N = (int)x.size(0), H = (int)x.size(2), W = (int)x.size(3);
+    const int HO = (int)((H + 2 * P - KH) / S + 1);
+    const int WO = (int)((W + 2 * P - KW) / S + 1);
+    auto gc = gout.contiguous(at::MemoryFormat::ChannelsLast);
+    TORCH_CHECK(gc.scalar_type() == x.scalar_type() && gc.size(0) == N &&
+                gc.size(1) == C && gc.size(2) == HO && gc.size(3) == WO,
+                "bn_act_pool_bwd: gout does not match the pooled shape");
+    TORCH_CHECK(idx.scalar_type() == at::kByte && idx.is_contiguous() &&
+                idx.numel() == (int64_t)N * HO * WO * C,
+                "bn_act_pool_bwd: argmax bytes do not match the pooled shape");
+    auto fopts = x.options().dtype(at::kFloat);
+    auto ws = at::empty({4 * C}, fopts);
+    const bool direct = gw_out.has_value() && gw_out->numel() == C;
+    auto gw = direct ? *gw_out : at::empty({C}, fopts);
+    auto gb = direct ? *gb_out : at::empty({C}, fopts);
+    auto gx = at::empty_like(x);
+    auto stream = cur_stream();
+    const int NB = fda::bn_relu_maxpool_bwd_blocks(N, H);
+    auto part = at::empty({NB, 2, C}, fopts);
+    fda::bn_relu_maxpool_bwd_stats_launch(
+        gc.data_ptr(), idx.data_ptr<uint8_t>(), x.data_ptr(),
+        save_mean.data_ptr<float>(), save_invstd.data_ptr<float>(),
+        weight.data_ptr<float>(), bias.data_ptr<float>(),
+        part.data_ptr<float>(), N, H, W, (int)C, HO, WO, (int)KH, (int)KW,
+        (int)S, (int)P, dt_of(x), stream);
+    fda::bn_bwd_finalize_from_partials_launch(
+        part.data_ptr<float>(), NB, ws.data_ptr<float>(),
+        gw.data_ptr<float>(), gb.data_ptr<float>(), rows, (int)C, training,
+        direct, stream);
+    fda::bn_relu_maxpool_bwd_apply_launch(
+        gc.data_ptr(), idx.data_ptr<uint8_t>(), x.data_ptr(),
+        save_mean.data_ptr<float>(), save_invstd.data_ptr<float>(),
+        weight.data_ptr<float>(), bias.data_ptr<float>(),
+        ws.data_ptr<float>(), gx.data_ptr(), N, H, W, (int)C, HO, WO,
+        (int)KH, (int)KW, (int)S, (int)P, dt_of(x), stream);
+    return {gx, gw, gb};
 }
 
 std::tuple<at::Tensor, at::Tensor> maxpool_fwd(at::Tensor x, int64_t KH,
@@ -681,7 +801,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("training"),
           pybind11::arg("gw_out") = pybind11::none(),
           pybind11::arg("gb_out") = pybind11::none(),
-          pybind11::arg("want_gres") = false);
+          pybind11::arg("want_gres") = false,
+          pybind11::arg("bias") = pybind11::none());
+    m.def("bn_act_pool_supported", &bn_act_pool_supported);
+    m.def("bn_act_pool_fwd", &bn_act_pool_fwd, pybind11::arg("x"),
+          pybind11::arg("weight"), pybind11::arg("bias"),
+          pybind11::arg("running_mean"), pybind11::arg("running_var"),
+          pybind11::arg("training"), pybind11::arg("momentum"),
+          pybind11::arg("eps"), pybind11::arg("KH"), pybind11::arg("KW"),
+          pybind11::arg("S"), pybind11::arg("P"),
+          pybind11::arg("conv_part") = pybind11::none());
+    m.def("bn_act_pool_bwd", &bn_act_pool_bwd, pybind11::arg("gout"),
+          pybind11::arg("x"), pybind11::arg("weight"), pybind11::arg("bias"),
+          pybind11::arg("save_mean"), pybind11::arg("save_invstd"),
+          pybind11::arg("idx"), pybind11::arg("KH"), pybind11::arg("KW"),
+          pybind11::arg("S"), pybind11::arg("P"), pybind11::arg("training"),
+          pybind11::arg("gw_out") = pybind11::none(),
+          pybind11::arg("gb_out") = pybind11::none());
     m.def("maxpool_fwd", &maxpool_fwd);
     m.def("maxpool_bwd", &maxpool_bwd);
     m.def("gap_fwd", &gap_fwd);

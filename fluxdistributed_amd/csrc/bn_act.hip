@@ -82,50 +82,71 @@ __global__ void bn_stats_kernel(const T* __restrict__ x,
 }
 
 // Fold part[NB][2*chunkC] into two per-channel totals (s, q), then run a
-// per-channel epilogue — all in one launch. Block: 16 float4-lanes (64
-// channels) x 16 partial-subgroups, LDS tree over subgroups. chunkC must be
-// a multiple of 64 (all ResNet channel counts).
+// per-channel epilogue — all in one launch. The launch is latency-bound
+// (<= 1024 rows, written a moment earlier by other XCDs, so every load is
+// a trip to memory), so the shape is chosen to put every load in flight at
+// once: block = 4 float4-lanes (16 channels) x 64 partial-subgroups, grid =
+// chunkC/16, and each thread issues its (up to) FIN_ROWS row loads before
+// the first add. NB <= 512 is one batch; larger NB loops batches. The 64
+// subgroups fold by wave shuffles, then one LDS hop across the 4 waves.
+// chunkC must be a multiple of 16.
 struct BnTotals { float s, q; };
+
+constexpr int FIN_LANES = 4;     // float4 lanes per block -> 16 channels
+constexpr int FIN_SUBS = 64;     // partial-row subgroups per block
+constexpr int FIN_ROWS = 8;      // rows in flight per thread
+constexpr int FIN_CH = FIN_LANES * 4;
 
 template <typename EPI>
 __device__ __forceinline__ void bn_reduce_then(const float* __restrict__ part,
                                                int NB, int chunkC, int c_base,
                                                EPI&& epilogue) {
-    __shared__ float sm[2 * 1024];  // [sub][lane][4] for s and q
-    const int lane = threadIdx.x & 15;
-    const int sub = threadIdx.x >> 4;
-    const int cc = (blockIdx.x * 16 + lane) * 4;  // channel quad in chunk
+    __shared__ float sm[4][2 * FIN_CH];  // [wave][s(16) | q(16)]
+    const int lane = threadIdx.x & (FIN_LANES - 1);
+    const int sub = threadIdx.x >> 2;
+    const int cc = blockIdx.x * FIN_CH + lane * 4;  // channel quad in chunk
     float4 s = {0, 0, 0, 0}, q = {0, 0, 0, 0};
-    #pragma unroll 4
-    for (int b = sub; b < NB; b += 16) {
-        const float* p = part + (int64_t)b * 2 * chunkC;
-        const float4 a = *(const float4*)(p + cc);
-        const float4 z = *(const float4*)(p + chunkC + cc);
-        s.x += a.x; s.y += a.y; s.z += a.z; s.w += a.w;
-        q.x += z.x; q.y += z.y; q.z += z.z; q.w += z.w;
-    }
-    *(float4*)(sm + (sub * 16 + lane) * 4) = s;
-    *(float4*)(sm + 1024 + (sub * 16 + lane) * 4) = q;
-    __syncthreads();
-    #pragma unroll
-    for (int off = 8; off > 0; off >>= 1) {
-        if (sub < off) {
-            #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                sm[(sub * 16 + lane) * 4 + k] +=
-                    sm[((sub + off) * 16 + lane) * 4 + k];
-                sm[1024 + (sub * 16 + lane) * 4 + k] +=
-                    sm[1024 + ((sub + off) * 16 + lane) * 4 + k];
+    for (int b0 = sub; b0 < NB; b0 += FIN_SUBS * FIN_ROWS) {
+        float4 a[FIN_ROWS], z[FIN_ROWS];
+        #pragma unroll
+        for (int j = 0; j < FIN_ROWS; ++j) {
+            const int b = b0 + j * FIN_SUBS;
+            a[j] = z[j] = float4{0, 0, 0, 0};
+            if (b < NB) {
+                const float* p = part + (int64_t)b * 2 * chunkC;
+                a[j] = *(const float4*)(p + cc);
+                z[j] = *(const float4*)(p + chunkC + cc);
             }
         }
-        __syncthreads();
+        #pragma unroll
+        for (int j = 0; j < FIN_ROWS; ++j) {
+            s.x += a[j].x; s.y += a[j].y; s.z += a[j].z; s.w += a[j].w;
+            q.x += z[j].x; q.y += z[j].y; q.z += z[j].z; q.w += z[j].w;
+        }
     }
-    if (sub == 0) {
+    // a wave holds 16 subgroups x 4 lanes: fold the subgroups by xor-shuffle
+    float v[8] = {s.x, s.y, s.z, s.w, q.x, q.y, q.z, q.w};
+    #pragma unroll
+    for (int off = FIN_LANES; off < WAVE; off <<= 1) {
+        #pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] += __shfl_xor(v[k], off, WAVE);
+    }
+    const int wave = threadIdx.x / WAVE;
+    if ((threadIdx.x & (WAVE - 1)) < FIN_LANES) {
         #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            BnTotals t{sm[(lane * 4 + k)], sm[1024 + lane * 4 + k]};
-            epilogue(c_base + cc + k, t);
+            sm[wave][lane * 4 + k] = v[k];
+            sm[wave][FIN_CH + lane * 4 + k] = v[4 + k];
         }
+    }
+    __syncthreads();
+    // one thread per channel: the epilogue's own loads run 16 wide
+    if (threadIdx.x < FIN_CH) {
+        const int t = threadIdx.x;
+        BnTotals tot{sm[0][t] + sm[1][t] + sm[2][t] + sm[3][t],
+                     sm[0][FIN_CH + t] + sm[1][FIN_CH + t] +
+                         sm[2][FIN_CH + t] + sm[3][FIN_CH + t]};
+        epilogue(c_base + blockIdx.x * FIN_CH + t, tot);
     }
 }
 
@@ -145,9 +166,9 @@ __global__ void bn_fwd_reduce_finalize_kernel(
         rv[c] += momentum * (var * unbias - rv[c]);
         save_mean[c] = mean;
         save_invstd[c] = invstd;
-        const float scale = weight[c] * invstd;
+        const float scale = bn_scale_of(weight[c], invstd);
         ws[2 * C + c] = scale;
-        ws[3 * C + c] = bias[c] - mean * scale;
+        ws[3 * C + c] = bn_shift_of(bias[c], mean, scale);
     });
 }
 
@@ -180,9 +201,9 @@ __global__ void bn_eval_finalize_kernel(float* __restrict__ ws,
     const float invstd = rsqrtf(rv[c] + eps);
     save_mean[c] = mean;
     save_invstd[c] = invstd;
-    const float scale = weight[c] * invstd;
+    const float scale = bn_scale_of(weight[c], invstd);
     ws[2 * C + c] = scale;
-    ws[3 * C + c] = bias[c] - mean * scale;
+    ws[3 * C + c] = bn_shift_of(bias[c], mean, scale);
 }
 
 template <typename T, int V, bool RELU, bool RES>
@@ -200,7 +221,7 @@ __global__ void bn_apply_kernel(const T* __restrict__ x,
         if constexpr (RES) *(uint4*)rv_ = ((const uint4*)res)[i];
         #pragma unroll
         for (int k = 0; k < V; ++k) {
-            float v = load_f32(xv + k) * scale[c0 + k] + shift[c0 + k];
+            float v = bn_affine(load_f32(xv + k), scale[c0 + k], shift[c0 + k]);
             if constexpr (RES) v += load_f32(rv_ + k);
             if constexpr (RELU) v = fmaxf(v, 0.f);
             store_f32(ov + k, v);
@@ -211,12 +232,20 @@ __global__ void bn_apply_kernel(const T* __restrict__ x,
 
 // ---- backward -------------------------------------------------------------
 
-template <typename T, int V, bool RELU>
+// XMASK (non-residual ReLU BN only): the ReLU mask comes from the recomputed
+// activation (bn_relu_positive: the sign the rounded, stored relu(x*scale+
+// shift) has) instead of a read of `out` — x and
+// the statistics are loaded anyway, so the `out` pass bought only a sign.
+// The expression is the forward's (fda_common.h), so the mask is the same
+// bit for bit. `out` is not touched in that variant.
+template <typename T, int V, bool RELU, bool XMASK = false>
 __global__ void bn_bwd_stats_kernel(const T* __restrict__ gout,
                                     const T* __restrict__ x,
                                     const T* __restrict__ out,
                                     const float* __restrict__ mean,
                                     const float* __restrict__ invstd,
+                                    const float* __restrict__ weight,
+                                    const float* __restrict__ bias,
                                     float* __restrict__ part, int64_t rows,
                                     int C, int c_base, int chunkC) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -226,23 +255,31 @@ __global__ void bn_bwd_stats_kernel(const T* __restrict__ gout,
     const int sub_r = threadIdx.x / tpr;
     const int c0 = c_base + lane_c * V;
 
-    float mu[V], is[V], sg[V], sgx[V];
+    float mu[V], is[V], sg[V], sgx[V], sc[V], sh[V];
     #pragma unroll
     for (int k = 0; k < V; ++k) {
         mu[k] = mean[c0 + k];
         is[k] = invstd[c0 + k];
         sg[k] = sgx[k] = 0.f;
+        if constexpr (XMASK) {
+            sc[k] = bn_scale_of(weight[c0 + k], is[k]);
+            sh[k] = bn_shift_of(bias[c0 + k], mu[k], sc[k]);
+        }
     }
     for (int64_t r = (int64_t)blockIdx.x * rpb + sub_r; r < rows;
          r += (int64_t)gridDim.x * rpb) {
         T gv[V], xv[V], ov[V];
         *(uint4*)gv = *(const uint4*)(gout + r * C + c0);
         *(uint4*)xv = *(const uint4*)(x + r * C + c0);
-        if constexpr (RELU) *(uint4*)ov = *(const uint4*)(out + r * C + c0);
+        if constexpr (RELU && !XMASK)
+            *(uint4*)ov = *(const uint4*)(out + r * C + c0);
         #pragma unroll
         for (int k = 0; k < V; ++k) {
             float g = load_f32(gv + k);
-            if constexpr (RELU) g = load_f32(ov + k) > 0.f ? g : 0.f;
+            if constexpr (XMASK)
+                g = bn_relu_positive<T>(load_f32(xv + k), sc[k], sh[k]) ? g : 0.f;
+            else if constexpr (RELU)
+                g = load_f32(ov + k) > 0.f ? g : 0.f;
             const float xhat = (load_f32(xv + k) - mu[k]) * is[k];
             sg[k] += g;
             sgx[k] += g * xhat;
@@ -272,13 +309,14 @@ __global__ void bn_bwd_stats_kernel(const T* __restrict__ gout,
     }
 }
 
-template <typename T, int V, bool RELU>
+template <typename T, int V, bool RELU, bool XMASK = false>
 __global__ void bn_bwd_apply_kernel(const T* __restrict__ gout,
                                     const T* __restrict__ x,
                                     const T* __restrict__ out,
                                     const float* __restrict__ mean,
                                     const float* __restrict__ invstd,
                                     const float* __restrict__ weight,
+                                    const float* __restrict__ bias,
                                     const float* __restrict__ k1,
                                     const float* __restrict__ k2,
                                     T* __restrict__ gx,
@@ -294,14 +332,20 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ gout,
         T gv[V], xv[V], ov[V], rv_[V], mv[V];
         *(uint4*)gv = ((const uint4*)gout)[i];
         *(uint4*)xv = ((const uint4*)x)[i];
-        if constexpr (RELU) *(uint4*)ov = ((const uint4*)out)[i];
+        if constexpr (RELU && !XMASK) *(uint4*)ov = ((const uint4*)out)[i];
         #pragma unroll
         for (int k = 0; k < V; ++k) {
             const int c = c0 + k;
             float g = load_f32(gv + k);
-            if constexpr (RELU) g = load_f32(ov + k) > 0.f ? g : 0.f;
-            store_f32(mv + k, g);
             const float is = invstd[c];
+            if constexpr (XMASK) {
+                const float sc = bn_scale_of(weight[c], is);
+                const float sh = bn_shift_of(bias[c], mean[c], sc);
+                g = bn_relu_positive<T>(load_f32(xv + k), sc, sh) ? g : 0.f;
+            } else if constexpr (RELU) {
+                g = load_f32(ov + k) > 0.f ? g : 0.f;
+            }
+            store_f32(mv + k, g);
             const float xhat = (load_f32(xv + k) - mean[c]) * is;
             const float r = (g - k1[c] - xhat * k2[c]) * weight[c] * is;
             store_f32(rv_ + k, r);
@@ -351,7 +395,7 @@ void bn_stats_launch(const void* x, float* ws, float* part,
             hipLaunchKernelGGL((bn_stats_kernel<float, 4>), dim3(grid),
                                dim3(256), shmem, s, (const float*)x, part,
                                rows, C, c_base, cc);
-        hipLaunchKernelGGL(bn_fwd_reduce_finalize_kernel, dim3(cc / 64),
+        hipLaunchKernelGGL(bn_fwd_reduce_finalize_kernel, dim3(cc / FIN_CH),
                            dim3(256), 0, s, part, weight, bias, running_mean,
                            running_var, save_mean, save_invstd, ws, grid, cc,
                            c_base, C, rows, momentum, eps);
@@ -397,22 +441,33 @@ void bn_bwd_stats_launch(const void* gout, const void* x, const void* out,
                          const float* save_mean, const float* save_invstd,
                          float* ws, float* part, float* gw, float* gb,
                          int64_t rows, int C, bool relu, bool training,
-                         bool accum_g, DT dt, hipStream_t s) {
+                         bool accum_g, DT dt, hipStream_t s,
+                         const float* weight, const float* bias) {
+    // weight+bias given (non-residual ReLU BN): mask from x, `out` unread
+    const bool xmask = relu && weight != nullptr && bias != nullptr;
     const int V = dt == DT::BF16 ? 8 : 4;
     int chunkC, nchunks, grid, shmem;
     stats_geom(C, V, rows, chunkC, nchunks, grid, shmem);
     for (int ch = 0; ch < nchunks; ++ch) {
         const int c_base = ch * chunkC;
         const int cc = (C - c_base) < chunkC ? (C - c_base) : chunkC;
-        #define FDA_BSTATS(T, VW, RELU_)                                        \
-            hipLaunchKernelGGL((bn_bwd_stats_kernel<T, VW, RELU_>), dim3(grid), \
-                               dim3(256), shmem, s, (const T*)gout,             \
-                               (const T*)x, (const T*)out, save_mean,           \
-                               save_invstd, part, rows, C, c_base, cc)
-        if (dt == DT::BF16) { if (relu) FDA_BSTATS(unsigned short, 8, true); else FDA_BSTATS(unsigned short, 8, false); }
-        else { if (relu) FDA_BSTATS(float, 4, true); else FDA_BSTATS(float, 4, false); }
+        #define FDA_BSTATS(T, VW, RELU_, XM_)                                   \
+            hipLaunchKernelGGL((bn_bwd_stats_kernel<T, VW, RELU_, XM_>),        \
+                               dim3(grid), dim3(256), shmem, s,                 \
+                               (const T*)gout, (const T*)x, (const T*)out,      \
+                               save_mean, save_invstd, weight, bias, part,      \
+                               rows, C, c_base, cc)
+        if (dt == DT::BF16) {
+            if (xmask) FDA_BSTATS(unsigned short, 8, true, true);
+            else if (relu) FDA_BSTATS(unsigned short, 8, true, false);
+            else FDA_BSTATS(unsigned short, 8, false, false);
+        } else {
+            if (xmask) FDA_BSTATS(float, 4, true, true);
+            else if (relu) FDA_BSTATS(float, 4, true, false);
+            else FDA_BSTATS(float, 4, false, false);
+        }
         #undef FDA_BSTATS
-        hipLaunchKernelGGL(bn_bwd_reduce_finalize_kernel, dim3(cc / 64),
+        hipLaunchKernelGGL(bn_bwd_reduce_finalize_kernel, dim3(cc / FIN_CH),
                            dim3(256), 0, s, part, ws, gw, gb, grid, cc,
                            c_base, C, rows, training ? 1 : 0,
                            accum_g ? 1 : 0);
@@ -423,6 +478,9 @@ void bn_bwd_stats_launch(const void* gout, const void* x, const void* out,
 // layer-1 shapes, and the single finalize launch only runs C/64 blocks —
 // one CU streaming ~2.4 MB serially (~15-20 us per BN measured as the
 // bn_*_reduce_finalize rows). Fold to NB2 rows first at full-grid width.
+// NB2 = 256 (bindings.cpp): a prefold thread then loads at most two rows
+// of a ~4700-row set, both in flight together, and the finalize that
+// follows reads four rows per thread in a single batch.
 __global__ __launch_bounds__(256) void bn_partial_prefold_kernel(
     const float* __restrict__ part, float* __restrict__ out, int NB,
     int NB2, int chunkC) {
@@ -432,6 +490,7 @@ __global__ __launch_bounds__(256) void bn_partial_prefold_kernel(
     const int cc = (blockIdx.x * 16 + lane) * 4;
     const int g = blockIdx.y;
     float4 sv = {0, 0, 0, 0}, qv = {0, 0, 0, 0};
+    #pragma unroll 2
     for (int b = g + sub * NB2; b < NB; b += 16 * NB2) {
         const float* p = part + (int64_t)b * 2 * chunkC;
         const float4 a = *(const float4*)(p + cc);
@@ -478,30 +537,51 @@ void bn_finalize_from_partials_launch(
     int64_t rows, int C, float momentum, float eps, hipStream_t s) {
     // partials produced by the conv epilogue ([NB][2][C], single chunk);
     // same reduce+finalize kernel the in-house stats pass feeds.
-    hipLaunchKernelGGL(bn_fwd_reduce_finalize_kernel, dim3(C / 64),
+    hipLaunchKernelGGL(bn_fwd_reduce_finalize_kernel, dim3(C / FIN_CH),
                        dim3(256), 0, s, part, weight, bias, rm, rv,
                        save_mean, save_invstd, ws, NB, C, 0, C, rows,
                        momentum, eps);
+}
+
+void bn_bwd_finalize_from_partials_launch(const float* part, int NB,
+                                          float* ws, float* gw, float* gb,
+                                          int64_t rows, int C, bool training,
+                                          bool accum_g, hipStream_t s) {
+    // partials produced by the fused BN+ReLU+pool backward stats pass
+    // ([NB][2][C], single chunk); same kernel bn_bwd_stats_launch feeds
+    hipLaunchKernelGGL(bn_bwd_reduce_finalize_kernel, dim3(C / FIN_CH),
+                       dim3(256), 0, s, part, ws, gw, gb, NB, C, 0, C, rows,
+                       training ? 1 : 0, accum_g ? 1 : 0);
 }
 
 void bn_bwd_apply_launch(const void* gout, const void* x, const void* out,
                          const float* save_mean, const float* save_invstd,
                          const float* weight, const float* ws, void* gx,
                          void* gres, int64_t rows, int C, bool relu,
-                         bool /*training*/, DT dt, hipStream_t s) {
+                         bool /*training*/, DT dt, hipStream_t s,
+                         const float* bias) {
+    // bias given (non-residual ReLU BN): mask from x, `out` unread
+    const bool xmask = relu && bias != nullptr && gres == nullptr;
     const int V = dt == DT::BF16 ? 8 : 4;
     const int64_t nvec = rows * C / V;
     int64_t blocks = (nvec + 255) / 256;
     const int grid = (int)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks));
     const float* k1 = ws + 2 * C;
     const float* k2 = ws + 3 * C;
-    #define FDA_BAPPLY(T, VW, RELU_)                                            \
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<T, VW, RELU_>), dim3(grid),     \
-                           dim3(256), 0, s, (const T*)gout, (const T*)x,        \
-                           (const T*)out, save_mean, save_invstd, weight, k1,   \
-                           k2, (T*)gx, (T*)gres, nvec, C)
-    if (dt == DT::BF16) { if (relu) FDA_BAPPLY(unsigned short, 8, true); else FDA_BAPPLY(unsigned short, 8, false); }
-    else { if (relu) FDA_BAPPLY(float, 4, true); else FDA_BAPPLY(float, 4, false); }
+    #define FDA_BAPPLY(T, VW, RELU_, XM_)                                       \
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<T, VW, RELU_, XM_>),            \
+                           dim3(grid), dim3(256), 0, s, (const T*)gout,         \
+                           (const T*)x, (const T*)out, save_mean, save_invstd,  \
+                           weight, bias, k1, k2, (T*)gx, (T*)gres, nvec, C)
+    if (dt == DT::BF16) {
+        if (xmask) FDA_BAPPLY(unsigned short, 8, true, true);
+        else if (relu) FDA_BAPPLY(unsigned short, 8, true, false);
+        else FDA_BAPPLY(unsigned short, 8, false, false);
+    } else {
+        if (xmask) FDA_BAPPLY(float, 4, true, true);
+        else if (relu) FDA_BAPPLY(float, 4, true, false);
+        else FDA_BAPPLY(float, 4, false, false);
+    }
     #undef FDA_BAPPLY
 }
 

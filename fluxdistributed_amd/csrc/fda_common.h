@@ -43,6 +43,76 @@ __device__ __forceinline__ void store_f32(T* p, float v) {
     else *(float*)p = v;
 }
 
+// One 16 B register load -> V floats (bf16: pure shifts/masks, exact). Going
+// through the uint4 value keeps the load a single dwordx4 the scheduler can
+// issue early; aliasing a T[V] array let the compiler split and sink it.
+template <typename T, int V>
+__device__ __forceinline__ void unpack_f32(const uint4& raw, float (&f)[V]) {
+    const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
+    if constexpr (sizeof(T) == 2) {
+        static_assert(V == 8, "16 B of bf16");
+        #pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            f[2 * i] = __uint_as_float(w[i] << 16);
+            f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+        }
+    } else {
+        static_assert(V == 4, "16 B of fp32");
+        #pragma unroll
+        for (int i = 0; i < 4; ++i) f[i] = __uint_as_float(w[i]);
+    }
+}
+
+// ---- BatchNorm affine, shared by every kernel that evaluates it ------------
+// The forward finalize, bn_apply and the kernels that recompute the ReLU
+// mask from x must agree bit for bit, so the expressions live here once.
+// Explicit intrinsics, so no kernel's result depends on how the compiler
+// chose to contract a*b+c there.
+__device__ __forceinline__ float bn_scale_of(float weight, float invstd) {
+    return __fmul_rn(weight, invstd);
+}
+__device__ __forceinline__ float bn_shift_of(float bias, float mean,
+                                             float scale) {
+    return __fmaf_rn(-mean, scale, bias);
+}
+__device__ __forceinline__ float bn_affine(float x, float scale, float shift) {
+    return __fmaf_rn(x, scale, shift);
+}
+// Round V floats through the storage dtype: what a store_f32 + load_f32
+// round trip yields, kept in registers.
+template <typename T, int V>
+__device__ __forceinline__ void round_storage(float (&f)[V]) {
+    if constexpr (sizeof(T) == 2) {
+        #pragma unroll
+        for (int i = 0; i < V; ++i) {
+            T t;
+            store_f32(&t, f[i]);
+            f[i] = load_f32(&t);
+        }
+    }
+}
+
+// True iff a non-residual ReLU BN's stored activation is positive: the value
+// bn_apply stores, max(affine(x), 0) rounded to the storage dtype, as the
+// backward kernels would load it from `out`.
+template <typename T>
+__device__ __forceinline__ bool bn_relu_positive(float x, float scale,
+                                                 float shift) {
+    T t;
+    store_f32(&t, fmaxf(bn_affine(x, scale, shift), 0.f));
+    return load_f32(&t) > 0.f;
+}
+
+// XCD-aware block remap (bijective for any grid size): blocks that share
+// `blockIdx % 8` share an L2, so give each such group a contiguous range
+// of logical ids. A pure locality choice — any mapping is correct.
+__device__ __forceinline__ unsigned xcd_contiguous_block(unsigned bid,
+                                                         unsigned nwg) {
+    const unsigned q = nwg / 8, r = nwg % 8, xcd = bid % 8;
+    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+    return base + bid / 8;
+}
+
 // ---- wave / block reductions ----------------------------------------------
 __device__ __forceinline__ float wave_reduce_sum(float v) {
     #pragma unroll

@@ -53,17 +53,22 @@ void bn_apply_launch(const void* x, const void* residual, void* out,
 
 // backward. ws layout (floats): [0,C) sum_g  [C,2C) sum_g_xhat
 //   [2C,3C) k1  [3C,4C) k2   (k's folded with invstd*gamma in finalize)
-// bwd: stats partials + fused reduce/finalize (gw, gb, k1/k2 into ws)
+// bwd: stats partials + fused reduce/finalize (gw, gb, k1/k2 into ws).
+// With weight+bias (stats) / bias (apply) on a non-residual ReLU BN the
+// ReLU mask is recomputed from x and `out` is never read.
 void bn_bwd_stats_launch(const void* gout, const void* x, const void* out,
                          const float* save_mean, const float* save_invstd,
                          float* ws, float* part, float* gw, float* gb,
                          int64_t rows, int C, bool relu, bool training,
-                         bool accum_g, DT dt, hipStream_t s);
+                         bool accum_g, DT dt, hipStream_t s,
+                         const float* weight = nullptr,
+                         const float* bias = nullptr);
 void bn_bwd_apply_launch(const void* gout, const void* x, const void* out,
                          const float* save_mean, const float* save_invstd,
                          const float* weight, const float* ws, void* gx,
                          void* gres, int64_t rows, int C, bool relu,
-                         bool training, DT dt, hipStream_t s);
+                         bool training, DT dt, hipStream_t s,
+                         const float* bias = nullptr);
 
 // MaxPool2d NHWC with saved argmax byte per output element
 void maxpool_fwd_launch(const void* x, void* out, uint8_t* idx, int N, int H,
@@ -72,6 +77,32 @@ void maxpool_fwd_launch(const void* x, void* out, uint8_t* idx, int N, int H,
 void maxpool_bwd_launch(const void* gout, const uint8_t* idx, void* gx, int N,
                         int H, int W, int C, int HO, int WO, int KH, int KW,
                         int S, int P, DT dt, hipStream_t s);
+
+// Fused stem tail: BN + ReLU + max-pool (pool.hip). Needs 256 % (C/V) == 0
+// (V = 8 bf16 / 4 fp32), KH*KW <= 255 and ceil(K/S) <= 2. fwd consumes the scale/shift the
+// forward finalize left in ws[2C..4C) and writes only the pooled tensor and
+// its argmax bytes. bwd stats writes [bn_relu_maxpool_bwd_blocks][2][C]
+// partials for bn_bwd_reduce_finalize; bwd apply reads k1/k2 from ws.
+void bn_relu_maxpool_fwd_launch(const void* x, const float* ws, void* out,
+                                uint8_t* idx, int N, int H, int W, int C,
+                                int HO, int WO, int KH, int KW, int S, int P,
+                                DT dt, hipStream_t s);
+int bn_relu_maxpool_bwd_blocks(int N, int H);
+void bn_relu_maxpool_bwd_stats_launch(
+    const void* gout, const uint8_t* idx, const void* x,
+    const float* save_mean, const float* save_invstd, const float* weight,
+    const float* bias, float* part, int N, int H, int W, int C, int HO,
+    int WO, int KH, int KW, int S, int P, DT dt, hipStream_t s);
+void bn_relu_maxpool_bwd_apply_launch(
+    const void* gout, const uint8_t* idx, const void* x,
+    const float* save_mean, const float* save_invstd, const float* weight,
+    const float* bias, const float* ws, void* gx, int N, int H, int W, int C,
+    int HO, int WO, int KH, int KW, int S, int P, DT dt, hipStream_t s);
+// fold [NB][2][C] backward partials: gw/gb (+= when accum), k1/k2 into ws
+void bn_bwd_finalize_from_partials_launch(const float* part, int NB,
+                                          float* ws, float* gw, float* gb,
+                                          int64_t rows, int C, bool training,
+                                          bool accum_g, hipStream_t s);
 
 // global average pool (NHWC): y[n][c] = mean_hw x; gx = gy/HW broadcast
 void gap_fwd_launch(const void* x, void* y, int N, int HW, int C, DT dt,

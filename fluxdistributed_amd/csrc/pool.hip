@@ -164,6 +164,417 @@ void maxpool_bwd_launch(const void* gout, const uint8_t* idx, void* gx, int N,
                            idx, (float*)gx, N, H, W, C, HO, WO, KH, KW, S, P);
 }
 
+// ---- fused stem tail: BN + ReLU + max-pool --------------------------------
+// The stem activation (N x 112 x 112 x 64) is the largest tensor of the
+// network and its passes run at HBM speed. Unfused, the post-ReLU tensor
+// and the full-resolution pool gradient exist only to be read back by the
+// next kernel. Fused: the forward reads x once and writes only the pooled
+// tensor + argmax bytes; the backward gathers the pooled gradient through
+// the argmax bytes and recomputes the ReLU mask from x, which it reads
+// anyway for xhat.
+//
+// Numerics are those of the unfused chain: the activation is rounded
+// through the storage dtype as bn_apply stores it (fda_common.h),
+// the max follows maxpool_fwd_kernel's rule (strict >, kh-then-kw scan,
+// first maximum wins), and the gathered gradient is rounded through the
+// storage dtype where maxpool_bwd_kernel stored it.
+//
+// All three kernels give a thread V fixed channels (256 % (C/V) == 0, checked
+// by the binding), so per-channel constants load once per thread.
+
+// fwd: one block per (n, ho) output row, threads over (wo, cv). KS > 0 is
+// a compile-time square window (KH == KW == KS): the window loop unrolls and
+// — because out-of-image taps load a clamped, in-image address and are
+// masked in the compare instead of skipped — all KS*KS loads are in flight
+// before the first use. With skip branches each tap waited out its own
+// memory latency in turn (75 us vs 34 us of traffic at the stem shape).
+// KS == 0 takes KH/KW at run time.
+template <typename T, int V, int KS>
+__global__ __launch_bounds__(256) void bn_relu_maxpool_fwd_kernel(
+    const T* __restrict__ x, const float* __restrict__ scale,
+    const float* __restrict__ shift, T* __restrict__ out,
+    uint8_t* __restrict__ idx, int N, int H, int W, int C, int HO, int WO,
+    int KH, int KW, int S, int P) {
+    const int CV = C / V;
+    // neighbouring output rows share input rows: keep them on one L2
+    const int row = (int)xcd_contiguous_block(blockIdx.x, gridDim.x);
+    const int ho = row % HO;
+    const int n = row / HO;
+    if (n >= N) return;
+    const int c0 = (threadIdx.x % CV) * V;
+    float sc[V], sh[V];
+    #pragma unroll
+    for (int k = 0; k < V; ++k) {
+        sc[k] = scale[c0 + k];
+        sh[k] = shift[c0 + k];
+    }
+    const int h0 = ho * S - P;
+    const T* ximg = x + (int64_t)n * H * W * C;
+    const int64_t orow = ((int64_t)n * HO + ho) * WO * C;
+
+    for (int t = threadIdx.x; t < WO * CV; t += blockDim.x) {
+        const int wo = t / CV;       // CV is a power of two: a shift
+        const int w0 = wo * S - P;
+        float best[V];
+        unsigned barg[V];
+        #pragma unroll
+        for (int k = 0; k < V; ++k) {
+            best[k] = -INFINITY;
+            barg[k] = 0;
+        }
+        // address of tap (kh, kw), clamped into the image; `ok` masks it
+        auto tap_ptr = [&](int kh, int kw, bool& ok) {
+            const int hi = h0 + kh, wi = w0 + kw;
+            ok = hi >= 0 && hi < H && wi >= 0 && wi < W;
+            return (const uint4*)(ximg + ((int64_t)min(max(hi, 0), H - 1) * W +
+                                          min(max(wi, 0), W - 1)) * C + c0);
+        };
+        // branch-free update: strict >, scan order, first maximum wins
+        auto tap_max = [&](const uint4& raw, bool ok, unsigned p) {
+            float f[V];
+            unpack_f32<T, V>(raw, f);
+            #pragma unroll
+            for (int k = 0; k < V; ++k)
+                f[k] = fmaxf(bn_affine(f[k], sc[k], sh[k]), 0.f);
+            round_storage<T, V>(f);   // the value bn_apply would have stored
+            #pragma unroll
+            for (int k = 0; k < V; ++k) {
+                const bool take = ok & (f[k] > best[k]);
+                best[k] = take ? f[k] : best[k];
+                barg[k] = take ? p : barg[k];
+            }
+        };
+        if constexpr (KS > 0) {
+            uint4 raw[KS * KS];
+            bool ok[KS * KS];
+            #pragma unroll
+            for (int j = 0; j < KS * KS; ++j)
+                raw[j] = *tap_ptr(j / KS, j % KS, ok[j]);
+            #pragma unroll
+            for (int j = 0; j < KS * KS; ++j) tap_max(raw[j], ok[j], j);
+        } else {
+            for (int kh = 0; kh < KH; ++kh)
+                for (int kw = 0; kw < KW; ++kw) {
+                    bool ok;
+                    const uint4 raw = *tap_ptr(kh, kw, ok);
+                    tap_max(raw, ok, (unsigned)(kh * KW + kw));
+                }
+        }
+        T ov[V];
+        uint64_t ib = 0;
+        #pragma unroll
+        for (int k = 0; k < V; ++k) {
+            store_f32(ov + k, best[k]);
+            ib |= (uint64_t)barg[k] << (8 * k);
+        }
+        const int64_t o = orow + (int64_t)wo * C + c0;
+        *(uint4*)(out + o) = *(uint4*)ov;
+        if constexpr (V == 8)
+            *(uint64_t*)(idx + o) = ib;
+        else
+            *(uint32_t*)(idx + o) = (uint32_t)ib;
+    }
+}
+
+// The gather of maxpool_bwd_kernel for V channels of input pixel (hi, wi):
+// sums the pooled gradients of the windows whose argmax byte names the
+// pixel, rounded through the storage dtype as that kernel stores it.
+// At most 2 x 2 windows cover a pixel (ceil(K/S) <= 2, checked by the
+// binding). All four are loaded — from a clamped, in-range address — and a
+// window that does not cover the pixel gets the impossible argmax code 256
+// instead of a skip branch, so the loads are in flight together; with skip
+// branches every window waited out its own memory latency in turn, which is
+// what bounds maxpool_bwd_kernel (104 us vs 34 us of traffic at the stem
+// shape). Accumulation order (ho, then wo) is that kernel's.
+struct PoolRowWin {   // the <= 2 pooled rows covering input row hi
+    int ho[2];        // clamped row index
+    int pbase[2];     // kh * KW, or 256 when the row does not cover hi
+};
+
+__device__ __forceinline__ PoolRowWin pool_row_windows(int hi, int HO, int KH,
+                                                       int KW, int S, int P) {
+    PoolRowWin r;
+    const int ho_lo = max(0, (hi + P - KH + S) / S);
+    const int ho_hi = min(HO - 1, (hi + P) / S);
+    #pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        const int ho = ho_lo + a;
+        const int kh = hi - (ho * S - P);
+        const bool ok = ho <= ho_hi && kh >= 0 && kh < KH;
+        r.ho[a] = min(ho, HO - 1);
+        r.pbase[a] = ok ? kh * KW : 256;
+    }
+    return r;
+}
+
+// grow/irow point at image n of the pooled gradient / argmax bytes.
+template <typename T, int V>
+__device__ __forceinline__ void pool_gather(
+    const T* __restrict__ grow, const uint8_t* __restrict__ irow,
+    const PoolRowWin& rw, int wi, int c0, int C, int WO, int KW, int S, int P,
+    float (&acc)[V]) {
+    const int wo_lo = max(0, (wi + P - KW + S) / S);
+    const int wo_hi = min(WO - 1, (wi + P) / S);
+    uint4 gv[4];
+    uint64_t ib[4];
+    unsigned code[4];
+    #pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        #pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int wo = wo_lo + b;
+            const int kw = wi - (wo * S - P);
+            const bool ok = wo <= wo_hi && kw >= 0 && kw < KW;
+            // pbase 256 keeps the sum >= 256: never equal to a byte
+            code[a * 2 + b] = ok ? (unsigned)(rw.pbase[a] + kw) : 256u;
+            const int64_t o =
+                ((int64_t)rw.ho[a] * WO + min(wo, WO - 1)) * C + c0;
+            gv[a * 2 + b] = *(const uint4*)(grow + o);
+            if constexpr (V == 8)
+                ib[a * 2 + b] = *(const uint64_t*)(irow + o);
+            else
+                ib[a * 2 + b] = *(const uint32_t*)(irow + o);
+        }
+    }
+    #pragma unroll
+    for (int k = 0; k < V; ++k) acc[k] = 0.f;
+    #pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float g[V];
+        unpack_f32<T, V>(gv[j], g);
+        // branch-free: a non-matching window adds an exact 0
+        #pragma unroll
+        for (int k = 0; k < V; ++k)
+            acc[k] += (unsigned)((ib[j] >> (8 * k)) & 0xffu) == code[j]
+                          ? g[k] : 0.f;
+    }
+    round_storage<T, V>(acc);
+}
+
+// bwd stats: sum_g and sum_g*xhat of the masked, gathered gradient into
+// part[block][2][C] — the layout bn_bwd_reduce_finalize_kernel folds. Each
+// block walks a contiguous range of (n, hi) input rows, so the pooled rows
+// it gathers from are fetched once.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_stats_kernel(
+    const T* __restrict__ gout, const uint8_t* __restrict__ idx,
+    const T* __restrict__ x, const float* __restrict__ mean,
+    const float* __restrict__ invstd, const float* __restrict__ weight,
+    const float* __restrict__ bias, float* __restrict__ part, int N, int H,
+    int W, int C, int HO, int WO, int KH, int KW, int S, int P,
+    int rows_per_block) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];  // 256*V
+    const int CV = C / V;
+    const int rpb = blockDim.x / CV;
+    const int lane_c = threadIdx.x % CV;
+    const int sub_r = threadIdx.x / CV;
+    const int c0 = lane_c * V;
+
+    float mu[V], is[V], sc[V], sh[V], sg[V], sgx[V];
+    #pragma unroll
+    for (int k = 0; k < V; ++k) {
+        mu[k] = mean[c0 + k];
+        is[k] = invstd[c0 + k];
+        sc[k] = bn_scale_of(weight[c0 + k], is[k]);
+        sh[k] = bn_shift_of(bias[c0 + k], mu[k], sc[k]);
+        sg[k] = sgx[k] = 0.f;
+    }
+    const int NR = N * H;
+    const int r_begin = blockIdx.x * rows_per_block;
+    const int r_end = min(NR, r_begin + rows_per_block);
+    for (int row = r_begin; row < r_end; ++row) {
+        const int hi = row % H;
+        const int n = row / H;
+        const PoolRowWin rw = pool_row_windows(hi, HO, KH, KW, S, P);
+        const T* grow = gout + (int64_t)n * HO * WO * C;
+        const uint8_t* irow = idx + (int64_t)n * HO * WO * C;
+        const T* xrow = x + (int64_t)row * W * C;
+        #pragma unroll 2
+        for (int wi = sub_r; wi < W; wi += rpb) {
+            const uint4 xraw = *(const uint4*)(xrow + (int64_t)wi * C + c0);
+            float g[V], xf8[V];
+            pool_gather<T, V>(grow, irow, rw, wi, c0, C, WO, KW, S, P, g);
+            unpack_f32<T, V>(xraw, xf8);
+            #pragma unroll
+            for (int k = 0; k < V; ++k) {
+                const float xf = xf8[k];
+                const float gm =
+                    bn_relu_positive<T>(xf, sc[k], sh[k]) ? g[k] : 0.f;
+                const float xhat = (xf - mu[k]) * is[k];
+                sg[k] += gm;
+                sgx[k] += gm * xhat;
+            }
+        }
+    }
+    float* outp = part + (int64_t)blockIdx.x * 2 * C;
+    #pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+        float* loc = pass == 0 ? sg : sgx;
+        #pragma unroll
+        for (int k = 0; k < V; ++k) smem[threadIdx.x * V + k] = loc[k];
+        __syncthreads();
+        if (sub_r == 0) {
+            float acc[V];
+            #pragma unroll
+            for (int k = 0; k < V; ++k) acc[k] = 0.f;
+            for (int rr = 0; rr < rpb; ++rr) {
+                const float* src = smem + (rr * CV + lane_c) * V;
+                #pragma unroll
+                for (int k = 0; k < V; ++k) acc[k] += src[k];
+            }
+            #pragma unroll
+            for (int k = 0; k < V; ++k)
+                outp[pass * C + lane_c * V + k] = acc[k];
+        }
+        __syncthreads();
+    }
+}
+
+// bwd apply: one block per (n, hi) input row; writes gx for the stem wgrad.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_apply_kernel(
+    const T* __restrict__ gout, const uint8_t* __restrict__ idx,
+    const T* __restrict__ x, const float* __restrict__ mean,
+    const float* __restrict__ invstd, const float* __restrict__ weight,
+    const float* __restrict__ bias, const float* __restrict__ k1,
+    const float* __restrict__ k2, T* __restrict__ gx, int N, int H, int W,
+    int C, int HO, int WO, int KH, int KW, int S, int P) {
+    const int CV = C / V;
+    const int row = (int)xcd_contiguous_block(blockIdx.x, gridDim.x);
+    const int hi = row % H;
+    const int n = row / H;
+    if (n >= N) return;
+    const int c0 = (threadIdx.x % CV) * V;
+
+    float mu[V], is[V], sc[V], sh[V], wk[V], a1[V], a2[V];
+    #pragma unroll
+    for (int k = 0; k < V; ++k) {
+        mu[k] = mean[c0 + k];
+        is[k] = invstd[c0 + k];
+        wk[k] = weight[c0 + k];
+        sc[k] = bn_scale_of(wk[k], is[k]);
+        sh[k] = bn_shift_of(bias[c0 + k], mu[k], sc[k]);
+        a1[k] = k1[c0 + k];
+        a2[k] = k2[c0 + k];
+    }
+    const PoolRowWin rw = pool_row_windows(hi, HO, KH, KW, S, P);
+    const T* grow = gout + (int64_t)n * HO * WO * C;
+    const uint8_t* irow = idx + (int64_t)n * HO * WO * C;
+    const T* xrow = x + (int64_t)row * W * C;
+    T* gxrow = gx + (int64_t)row * W * C;
+
+    #pragma unroll 2
+    for (int t = threadIdx.x; t < W * CV; t += blockDim.x) {
+        const int wi = t / CV;
+        T rv[V];
+        const uint4 xraw = *(const uint4*)(xrow + (int64_t)wi * C + c0);
+        float g[V], xf8[V];
+        pool_gather<T, V>(grow, irow, rw, wi, c0, C, WO, KW, S, P, g);
+        unpack_f32<T, V>(xraw, xf8);
+        #pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const float xf = xf8[k];
+            const float gm =
+                bn_relu_positive<T>(xf, sc[k], sh[k]) ? g[k] : 0.f;
+            const float xhat = (xf - mu[k]) * is[k];
+            // bn_bwd_apply_kernel's expression
+            const float r = (gm - a1[k] - xhat * a2[k]) * wk[k] * is[k];
+            store_f32(rv + k, r);
+        }
+        *(uint4*)(gxrow + (int64_t)wi * C + c0) = *(uint4*)rv;
+    }
+}
+
+void bn_relu_maxpool_fwd_launch(const void* x, const float* ws, void* out,
+                                uint8_t* idx, int N, int H, int W, int C,
+                                int HO, int WO, int KH, int KW, int S, int P,
+                                DT dt, hipStream_t s) {
+    const float* scale = ws + 2 * C;
+    const float* shift = ws + 3 * C;
+    const unsigned rows = (unsigned)((int64_t)N * HO);
+    #define FDA_BNPOOL(T, VW, KS_)                                              \
+        hipLaunchKernelGGL((bn_relu_maxpool_fwd_kernel<T, VW, KS_>),            \
+                           dim3(rows), dim3(256), 0, s, (const T*)x, scale,     \
+                           shift, (T*)out, idx, N, H, W, C, HO, WO, KH, KW, S,  \
+                           P)
+    const int ks = KH == KW && (KH == 3 || KH == 2) ? KH : 0;
+    if (dt == DT::BF16) {
+        if (ks == 3) FDA_BNPOOL(unsigned short, 8, 3);
+        else if (ks == 2) FDA_BNPOOL(unsigned short, 8, 2);
+        else FDA_BNPOOL(unsigned short, 8, 0);
+    } else {
+        if (ks == 3) FDA_BNPOOL(float, 4, 3);
+        else if (ks == 2) FDA_BNPOOL(float, 4, 2);
+        else FDA_BNPOOL(float, 4, 0);
+    }
+    #undef FDA_BNPOOL
+}
+
+// Grid of the fused bwd stats pass == rows of its partial buffer. Capped at
+// 1024 blocks (4 per CU): each row costs a block a dependent gather, so it
+// wants more waves in flight than the streaming stats pass's 512; the
+// finalize folds 1024 rows in two batches. Measured against a 512 cap at the
+// stem shape: stats kernel 107 vs 120 us, finalize 5.1 vs 5.3 us
+// (profiles/step_profile_r3.md).
+static inline void pool_stats_geom(int64_t NR, int& grid, int& rows_per_block) {
+    const int64_t cap = 1024;
+    rows_per_block = (int)((NR + cap - 1) / cap);
+    if (rows_per_block < 1) rows_per_block = 1;
+    grid = (int)((NR + rows_per_block - 1) / rows_per_block);
+    if (grid < 1) grid = 1;
+}
+
+int bn_relu_maxpool_bwd_blocks(int N, int H) {
+    int grid, rpb;
+    pool_stats_geom((int64_t)N * H, grid, rpb);
+    return grid;
+}
+
+void bn_relu_maxpool_bwd_stats_launch(
+    const void* gout, const uint8_t* idx, const void* x,
+    const float* save_mean, const float* save_invstd, const float* weight,
+    const float* bias, float* part, int N, int H, int W, int C, int HO,
+    int WO, int KH, int KW, int S, int P, DT dt, hipStream_t s) {
+    int grid, rpb;
+    pool_stats_geom((int64_t)N * H, grid, rpb);
+    const int V = dt == DT::BF16 ? 8 : 4;
+    const int shmem = 256 * V * (int)sizeof(float);
+    if (dt == DT::BF16)
+        hipLaunchKernelGGL(
+            (bn_relu_maxpool_bwd_stats_kernel<unsigned short, 8>), dim3(grid),
+            dim3(256), shmem, s, (const unsigned short*)gout, idx,
+            (const unsigned short*)x, save_mean, save_invstd, weight, bias,
+            part, N, H, W, C, HO, WO, KH, KW, S, P, rpb);
+    else
+        hipLaunchKernelGGL((bn_relu_maxpool_bwd_stats_kernel<float, 4>),
+                           dim3(grid), dim3(256), shmem, s,
+                           (const float*)gout, idx, (const float*)x,
+                           save_mean, save_invstd, weight, bias, part, N, H,
+                           W, C, HO, WO, KH, KW, S, P, rpb);
+}
+
+void bn_relu_maxpool_bwd_apply_launch(
+    const void* gout, const uint8_t* idx, const void* x,
+    const float* save_mean, const float* save_invstd, const float* weight,
+    const float* bias, const float* ws, void* gx, int N, int H, int W, int C,
+    int HO, int WO, int KH, int KW, int S, int P, DT dt, hipStream_t s) {
+    const float* k1 = ws + 2 * C;
+    const float* k2 = ws + 3 * C;
+    const unsigned rows = (unsigned)((int64_t)N * H);
+    if (dt == DT::BF16)
+        hipLaunchKernelGGL(
+            (bn_relu_maxpool_bwd_apply_kernel<unsigned short, 8>), dim3(rows),
+            dim3(256), 0, s, (const unsigned short*)gout, idx,
+            (const unsigned short*)x, save_mean, save_invstd, weight, bias,
+            k1, k2, (unsigned short*)gx, N, H, W, C, HO, WO, KH, KW, S, P);
+    else
+        hipLaunchKernelGGL((bn_relu_maxpool_bwd_apply_kernel<float, 4>),
+                           dim3(rows), dim3(256), 0, s, (const float*)gout,
+                           idx, (const float*)x, save_mean, save_invstd,
+                           weight, bias, k1, k2, (float*)gx, N, H, W, C, HO,
+                           WO, KH, KW, S, P);
+}
+
 }  // namespace fda
 
 namespace fda {

@@ -9,14 +9,15 @@ Conv weights are bias-free, as in the reference (Flux convs with
 `bias=Flux.Zeros` — see SURVEY.md §2.4).
 """
 
-from typing import List, Optional, Type
+import os
+from typing import List, Optional, Tuple, Type
 
 import torch
 import torch.nn as nn
 
 from ..ops.linear import FdaLinear
-from ..ops.functional import (batch_norm_act, MaxPool2d,
-                              GlobalAvgPool)
+from ..ops.functional import (batch_norm_act, batch_norm_act_pool,
+                              bn_act_pool_fusible, MaxPool2d, GlobalAvgPool)
 
 
 class FusedBNAct(nn.Module):
@@ -58,9 +59,21 @@ class FusedBNAct(nn.Module):
         super()._load_from_state_dict(*args, **kw)
 
     def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None,
-                defer_gres: bool = False):
+                defer_gres: bool = False,
+                pool: Optional[Tuple[int, int, int]] = None):
+        """`pool=(kernel, stride, padding)` also applies a max-pool to the
+        result inside the same native op (ReLU BN without residual only;
+        the caller checks bn_act_pool_fusible)."""
         if self.training:
             self._nbt_pending += 1
+        if pool is not None:
+            if not self.relu or residual is not None:
+                raise ValueError("pool fusion needs a ReLU BN without residual")
+            return batch_norm_act_pool(
+                x, self.weight, self.bias, self.running_mean,
+                self.running_var, self.training, self.momentum, self.eps,
+                *pool,
+            )
         return batch_norm_act(
             x, self.weight, self.bias, self.running_mean, self.running_var,
             self.training, self.momentum, self.eps, self.relu, residual,
@@ -203,8 +216,26 @@ class ResNet(nn.Module):
                 nn.init.normal_(m.weight, 0, 0.01)
                 nn.init.zeros_(m.bias)
 
+    def _stem_pool(self, y: torch.Tensor) -> Optional[Tuple[int, int, int]]:
+        """Pool geometry when the stem tail (bn1 + ReLU + maxpool) can run
+        as one native op, else None. FLUXDIST_STEM_FUSE=0 turns it off."""
+        mp = self.maxpool
+        if type(mp) is not MaxPool2d or not self.bn1.relu:
+            return None
+        if os.environ.get("FLUXDIST_STEM_FUSE", "1") == "0":
+            return None
+        geom = (mp.kernel_size, mp.stride, mp.padding)
+        if not (y.is_cuda and all(isinstance(g, int) for g in geom)):
+            return None
+        return geom if bn_act_pool_fusible(y, *geom) else None
+
     def forward(self, x):
-        x = self.maxpool(self.bn1(self.conv1(x)))
+        y = self.conv1(x)
+        pool = self._stem_pool(y)
+        if pool is not None:
+            x = self.bn1(y, pool=pool)
+        else:
+            x = self.maxpool(self.bn1(y))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         x = self.avgpool(x)
         return self.fc(x)

@@ -281,8 +281,11 @@ def _arena_for(weight) -> _WtArena:
 
 
 class _FdaConv2d(torch.autograd.Function):
-    """Forward + input-grad on the native implicit-GEMM kernels; weight-grad
-    via the library (aten convolution_backward with weight-only mask)."""
+    """Forward, input-grad and weight-grad on the native implicit-GEMM
+    kernels. The weight-grad lands in an fp32 workspace and, when the
+    weight lives in a fused optimizer's flat buffer, is flushed straight
+    into its G slice. FLUXDIST_WGRAD=miopen routes the weight-grad alone to
+    the library (aten convolution_backward with a weight-only mask)."""
 
     @staticmethod
     def forward(ctx, x, weight, stride, padding, want_stats):

@@ -8,6 +8,7 @@ Numerics contract (tests/test_ops_gpu.py): every native kernel is compared
 against the plain fp32 PyTorch composition of the same op.
 """
 
+import os
 from typing import Optional
 
 import torch
@@ -193,10 +194,14 @@ class _BNAct(torch.autograd.Function):
         gb_sl = flat_grad_slice(bias) if bias is not None else None
         direct = gw_sl is not None and gb_sl is not None
         want_gres = ctx.has_residual and ctx.relu
+        # bias lets a non-residual ReLU BN recompute its mask from x (which
+        # both kernels load anyway) instead of reading `out` twice
+        mask_bias = bias if _mask_from_x() else None
         gx, gw, gb, gres_k = C.bn_act_bwd(
             grad_out.contiguous(memory_format=torch.channels_last),
             x, weight, save_mean, save_invstd, out, ctx.relu, ctx.training,
             gw_sl if direct else None, gb_sl if direct else None, want_gres,
+            mask_bias,
         )
         if direct:
             from ..parallel.bucketing import notify_grad_written
@@ -215,6 +220,102 @@ class _BNAct(torch.autograd.Function):
             stash_junction_gres(ctx.res_key, gres)
             gres = None     # the conv dgrad epilogue folds it into dx
         return gx, gw, gb, None, None, None, None, None, None, gres, None
+
+
+def _mask_from_x() -> bool:
+    """FLUXDIST_BN_XMASK=0 keeps the backward ReLU mask on the saved output
+    (A/B knob, docs/kernels.md)."""
+    return os.environ.get("FLUXDIST_BN_XMASK", "1") != "0"
+
+
+class _BNActPool(torch.autograd.Function):
+    """BN + ReLU + max-pool as one op (the ResNet stem tail): neither the
+    full-resolution activation nor the full-resolution pool gradient is
+    ever written. Saves x, the BN parameters/statistics and the argmax
+    bytes; backward mirrors _BNAct.backward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, training,
+                momentum, eps, kernel, stride, padding):
+        C = require_native("batch_norm_act_pool")
+        from .conv import take_conv_stats
+
+        conv_part = take_conv_stats(x) if training else None
+        x = x.contiguous(memory_format=torch.channels_last)
+        out, idx, save_mean, save_invstd = C.bn_act_pool_fwd(
+            x, weight, bias, running_mean, running_var, training, momentum,
+            eps, kernel, kernel, stride, padding, conv_part,
+        )
+        ctx.save_for_backward(x, weight, bias, save_mean, save_invstd, idx)
+        ctx.geom = (kernel, stride, padding)
+        ctx.training = training
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, weight, bias, save_mean, save_invstd, idx = ctx.saved_tensors
+        k, s, p = ctx.geom
+        C = require_native("batch_norm_act_pool")
+        # direct grads into the fused optimizer's flat G slices, as in
+        # _BNAct.backward
+        from .fused_optim import flat_grad_slice
+
+        gw_sl = flat_grad_slice(weight)
+        gb_sl = flat_grad_slice(bias)
+        direct = gw_sl is not None and gb_sl is not None
+        gx, gw, gb = C.bn_act_pool_bwd(
+            grad_out.contiguous(memory_format=torch.channels_last),
+            x, weight, bias, save_mean, save_invstd, idx, k, k, s, p,
+            ctx.training,
+            gw_sl if direct else None, gb_sl if direct else None,
+        )
+        if direct:
+            from ..parallel.bucketing import notify_grad_written
+
+            notify_grad_written(weight)
+            notify_grad_written(bias)
+            gw = gb = None
+        return gx, gw, gb, None, None, None, None, None, None, None, None
+
+
+def bn_act_pool_fusible(x: torch.Tensor, kernel: int, stride: int,
+                        padding: int) -> bool:
+    """True when batch_norm_act_pool's native kernels take this input:
+    a GPU tensor in bf16/fp32 whose channel count and pool geometry the
+    fused kernels support (checked by the extension itself)."""
+    if not (_on_gpu(x) and x.dim() == 4
+            and x.dtype in (torch.bfloat16, torch.float32)):
+        return False
+    C = require_native("batch_norm_act_pool")
+    return bool(C.bn_act_pool_supported(
+        x.shape[1], x.dtype == torch.bfloat16, kernel, kernel, stride, padding))
+
+
+def batch_norm_act_pool(
+    x: torch.Tensor,
+    weight: torch.Tensor,
+    bias: torch.Tensor,
+    running_mean: torch.Tensor,
+    running_var: torch.Tensor,
+    training: bool,
+    momentum: float = 0.1,
+    eps: float = 1e-5,
+    kernel: int = 3,
+    stride: int = 2,
+    padding: int = 1,
+) -> torch.Tensor:
+    """max_pool2d(relu(BN(x))) in one native op; numerics are those of
+    batch_norm_act(relu=True) followed by max_pool2d, including which
+    element of a tied window wins. GPU only — callers check
+    bn_act_pool_fusible and otherwise run the two ops."""
+    if not bn_act_pool_fusible(x, kernel, stride, padding):
+        raise RuntimeError(
+            f"batch_norm_act_pool: unsupported input {tuple(x.shape)} "
+            f"{x.dtype} on {x.device} or pool k={kernel} s={stride} p={padding}")
+    return _BNActPool.apply(
+        x, weight, bias, running_mean, running_var, training, momentum, eps,
+        kernel, stride, padding,
+    )
 
 
 def batch_norm_act(
