@@ -372,127 +372,85 @@ void adam_step(at::Tensor P, at::Tensor G, at::Tensor M, at::Tensor V,
 // Tile geometry and split-K come from fda::conv_igemm_plan (the same
 // function the launcher obeys), so workspace shapes always match.
 
-// in-launch split-K: per-(m,n,zclass)-tile ticket counters, zeroed on the
-// stream ahead of the launch (guide Guideline 16)
-static unsigned* sk_tickets(const at::Tensor& ref, long ntiles,
-                            at::Tensor& keepalive, hipStream_t stream) {
-    keepalive = at::empty({ntiles}, ref.options().dtype(at::kInt));
-    unsigned* p = (unsigned*)keepalive.data_ptr<int>();
-    hipMemsetAsync(p, 0, sizeof(unsigned) * ntiles, stream);
-    return p;
-}
-
-
-at::Tensor conv_igemm_fwd(at::Tensor x, at::Tensor w,
-                          int64_t sy, int64_t sx, int64_t py, int64_t px) {
-    TORCH_CHECK(x.dim() == 4 && w.dim() == 4);
-    TORCH_CHECK(x.is_cuda() && w.is_cuda(),
+// Operand check shared by the five conv_igemm entry points. `act` is a 4-D
+// channels_last activation (x or dy); `other` is the second operand: a 4-D
+// channels_last tensor (w, or x for wgrad) or the 2-D contiguous
+// pre-transposed weight wt of dgrad. Both channel counts must be multiples
+// of 64.
+static void check_conv_operands(const at::Tensor& act, const at::Tensor& other,
+                                int64_t C, int64_t K) {
+    TORCH_CHECK(act.is_cuda() && other.is_cuda(),
                 "conv_igemm: device tensors required (a CPU tensor here "
                 "would fault the GPU with a host pointer)");
-    TORCH_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16,
+    TORCH_CHECK(act.scalar_type() == at::kBFloat16 &&
+                other.scalar_type() == at::kBFloat16,
                 "conv_igemm: bf16 only");
-    TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast),
-                "conv_igemm: x must be channels_last");
-    TORCH_CHECK(w.is_contiguous(at::MemoryFormat::ChannelsLast),
-                "conv_igemm: w must be channels_last");
+    TORCH_CHECK(act.dim() == 4 &&
+                act.is_contiguous(at::MemoryFormat::ChannelsLast),
+                "conv_igemm: activations must be 4-D channels_last");
+    TORCH_CHECK(other.dim() == 2
+                    ? other.is_contiguous()
+                    : other.dim() == 4 &&
+                      other.is_contiguous(at::MemoryFormat::ChannelsLast),
+                "conv_igemm: second operand must be 4-D channels_last, or "
+                "the 2-D contiguous transposed weight for dgrad");
+    TORCH_CHECK(C % 64 == 0 && K % 64 == 0,
+                "conv_igemm: C and K must be multiples of 64");
+}
+
+// forward, optionally with per-m-tile BN partials [tiles][2][K] (sum/sumsq
+// of the rounded output) that feed bn_finalize_from_partials; the partials
+// tensor is undefined when want_stats is false.
+static std::tuple<at::Tensor, at::Tensor> conv_igemm_fwd_impl(
+    const at::Tensor& x, const at::Tensor& w, int64_t sy, int64_t sx,
+    int64_t py, int64_t px, bool want_stats) {
+    TORCH_CHECK(x.dim() == 4 && w.dim() == 4);
     const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2),
               W = (int)x.size(3);
     const int K = (int)w.size(0), R = (int)w.size(2), S = (int)w.size(3);
+    check_conv_operands(x, w, C, K);
     TORCH_CHECK((int)w.size(1) == C, "channel mismatch");
-    TORCH_CHECK(C % 64 == 0 && K % 64 == 0,
-                "conv_igemm: C and K must be multiples of 64");
     const int P = (H + 2 * (int)py - R) / (int)sy + 1;
     const int Q = (W + 2 * (int)px - S) / (int)sx + 1;
     auto y = at::empty({N, K, P, Q},
                        x.options().memory_format(at::MemoryFormat::ChannelsLast));
+    const auto f32 = x.options().dtype(at::kFloat);
     const long M = (long)N * P * Q;
     int BM, BN, SK;
     fda::conv_igemm_plan(M, K, (long)R * S * (C / 64), 1, &BM, &BN, &SK);
+    at::Tensor part;
     if (SK > 1) {
-        auto part = at::empty({(long)SK * M * K},
-                              x.options().dtype(at::kFloat));
-        if (fda::conv_use_inlsk()) {
-            at::Tensor cnt_t;
-            unsigned* cnt = sk_tickets(x, ((M + BM - 1) / BM) * (K / BN),
-                                       cnt_t, cur_stream());
-            fda::conv_igemm_launch(x.data_ptr(), w.data_ptr(), y.data_ptr(),
-                                   N, H, W, C, K, P, Q, R, S, (int)sy,
-                                   (int)sx, (int)py, (int)px, false,
-                                   cur_stream(), nullptr,
-                                   part.data_ptr<float>(), SK, cnt);
-            return y;
-        }
+        // the combine kernel rounds to bf16 and writes the partials
+        auto skp = at::empty({(long)SK * M * K}, f32);
+        const int nb = fda::conv_skcombine_blocks(M, K);
+        if (want_stats) part = at::empty({nb, 2, K}, f32);
         fda::conv_igemm_launch(x.data_ptr(), w.data_ptr(), y.data_ptr(),
                                N, H, W, C, K, P, Q, R, S, (int)sy, (int)sx,
-                               (int)py, (int)px, false, cur_stream(), nullptr,
-                               part.data_ptr<float>(), SK);
-        fda::conv_skcombine_launch(part.data_ptr<float>(), y.data_ptr(),
-                                   nullptr, M, K, SK,
-                                   fda::conv_skcombine_blocks(M, K),
-                                   cur_stream());
-        return y;
+                               (int)py, (int)px, /*dgrad=*/false,
+                               cur_stream(), nullptr, skp.data_ptr<float>(),
+                               SK);
+        fda::conv_skcombine_launch(skp.data_ptr<float>(), y.data_ptr(),
+                                   want_stats ? part.data_ptr<float>() : nullptr,
+                                   M, K, SK, nb, cur_stream());
+        return {y, part};
     }
+    if (want_stats) part = at::empty({(M + BM - 1) / BM, 2, K}, f32);
     fda::conv_igemm_launch(x.data_ptr(), w.data_ptr(), y.data_ptr(),
                            N, H, W, C, K, P, Q, R, S, (int)sy, (int)sx,
-                           (int)py, (int)px, /*dgrad=*/false, cur_stream());
-    return y;
+                           (int)py, (int)px, /*dgrad=*/false, cur_stream(),
+                           want_stats ? part.data_ptr<float>() : nullptr);
+    return {y, part};
+}
+
+at::Tensor conv_igemm_fwd(at::Tensor x, at::Tensor w,
+                          int64_t sy, int64_t sx, int64_t py, int64_t px) {
+    return std::get<0>(conv_igemm_fwd_impl(x, w, sy, sx, py, px, false));
 }
 
 std::tuple<at::Tensor, at::Tensor> conv_igemm_fwd_stats(
     at::Tensor x, at::Tensor w, int64_t sy, int64_t sx, int64_t py,
     int64_t px) {
-    // forward + per-m-tile BN partials [mtiles][2][K] (sum/sumsq of the
-    // rounded output) — feeds bn_finalize_from_partials.
-    TORCH_CHECK(x.dim() == 4 && w.dim() == 4);
-    TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
-                x.is_contiguous(at::MemoryFormat::ChannelsLast));
-    TORCH_CHECK(w.is_contiguous(at::MemoryFormat::ChannelsLast));
-    const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2),
-              W = (int)x.size(3);
-    const int K = (int)w.size(0), R = (int)w.size(2), S = (int)w.size(3);
-    TORCH_CHECK(C % 64 == 0 && K % 64 == 0);
-    const int P = (H + 2 * (int)py - R) / (int)sy + 1;
-    const int Q = (W + 2 * (int)px - S) / (int)sx + 1;
-    const long M = (long)N * P * Q;
-    auto y = at::empty({N, K, P, Q},
-                       x.options().memory_format(at::MemoryFormat::ChannelsLast));
-    int BM, BN, SK;
-    fda::conv_igemm_plan(M, K, (long)R * S * (C / 64), 1, &BM, &BN, &SK);
-    if (SK > 1) {
-        auto skp = at::empty({(long)SK * M * K}, x.options().dtype(at::kFloat));
-        if (fda::conv_use_inlsk()) {
-            // reducer blocks write the stats partials like a SK=1 launch:
-            // [mtiles][2][K] with mtiles = grid.x
-            const long mtiles = (M + BM - 1) / BM;
-            auto part = at::empty({mtiles, 2, K}, x.options().dtype(at::kFloat));
-            at::Tensor cnt_t;
-            unsigned* cnt = sk_tickets(x, mtiles * (K / BN), cnt_t,
-                                       cur_stream());
-            fda::conv_igemm_launch(x.data_ptr(), w.data_ptr(), y.data_ptr(),
-                                   N, H, W, C, K, P, Q, R, S, (int)sy,
-                                   (int)sx, (int)py, (int)px, false,
-                                   cur_stream(), part.data_ptr<float>(),
-                                   skp.data_ptr<float>(), SK, cnt);
-            return {y, part};
-        }
-        const int nb = fda::conv_skcombine_blocks(M, K);
-        auto part = at::empty({nb, 2, K}, x.options().dtype(at::kFloat));
-        fda::conv_igemm_launch(x.data_ptr(), w.data_ptr(), y.data_ptr(),
-                               N, H, W, C, K, P, Q, R, S, (int)sy, (int)sx,
-                               (int)py, (int)px, false, cur_stream(), nullptr,
-                               skp.data_ptr<float>(), SK);
-        fda::conv_skcombine_launch(skp.data_ptr<float>(), y.data_ptr(),
-                                   part.data_ptr<float>(), M, K, SK, nb,
-                                   cur_stream());
-        return {y, part};
-    }
-    const long mtiles = (M + BM - 1) / BM;
-    auto part = at::empty({mtiles, 2, K}, x.options().dtype(at::kFloat));
-    fda::conv_igemm_launch(x.data_ptr(), w.data_ptr(), y.data_ptr(),
-                           N, H, W, C, K, P, Q, R, S, (int)sy, (int)sx,
-                           (int)py, (int)px, /*dgrad=*/false, cur_stream(),
-                           part.data_ptr<float>());
-    return {y, part};
+    return conv_igemm_fwd_impl(x, w, sy, sx, py, px, true);
 }
 
 at::Tensor conv_igemm_dgrad(at::Tensor dy, at::Tensor wt,
@@ -504,21 +462,17 @@ at::Tensor conv_igemm_dgrad(at::Tensor dy, at::Tensor wt,
     // the epilogue (residual-junction grad fusion, ops/conv.py).
     // dy: [N,K,P,Q] channels_last; wt: [R*S*C, K] row-major (pre-transposed
     // weight, k contiguous). Output dx: [N,C,H,W] channels_last.
-    TORCH_CHECK(dy.is_cuda() && wt.is_cuda());
-    TORCH_CHECK(dy.dim() == 4 && dy.scalar_type() == at::kBFloat16);
-    TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast));
-    TORCH_CHECK(wt.dim() == 2 && wt.is_contiguous() &&
-                wt.scalar_type() == at::kBFloat16);
+    TORCH_CHECK(dy.dim() == 4 && wt.dim() == 2);
     const int N = (int)dy.size(0), K = (int)dy.size(1), P = (int)dy.size(2),
               Q = (int)dy.size(3);
+    check_conv_operands(dy, wt, C, K);
     TORCH_CHECK(wt.size(0) == R * S * C && wt.size(1) == K, "wt shape mismatch");
-    TORCH_CHECK(C % 64 == 0 && K % 64 == 0,
-                "conv_igemm: C and K must be multiples of 64");
     auto dx = at::empty({N, C, H, W},
                         dy.options().memory_format(at::MemoryFormat::ChannelsLast));
     const void* accp = nullptr;
     if (accum.has_value() && accum->defined()) {
-        TORCH_CHECK(accum->is_contiguous(at::MemoryFormat::ChannelsLast) &&
+        TORCH_CHECK(accum->is_cuda() &&
+                    accum->is_contiguous(at::MemoryFormat::ChannelsLast) &&
                     accum->scalar_type() == at::kBFloat16 &&
                     accum->numel() == dx.numel(),
                     "dgrad accum tensor must be channels_last bf16 of dx's shape");
@@ -532,21 +486,10 @@ at::Tensor conv_igemm_dgrad(at::Tensor dy, at::Tensor wt,
     if (SK > 1) {
         auto skp = at::empty({(long)SK * M * C},
                              dy.options().dtype(at::kFloat));
-        if (fda::conv_use_inlsk() && accp == nullptr) {
-            at::Tensor cnt_t;
-            unsigned* cnt = sk_tickets(dy, ((M + BM - 1) / BM) * (C / BN),
-                                       cnt_t, cur_stream());
-            fda::conv_igemm_launch(dy.data_ptr(), wt.data_ptr(),
-                                   dx.data_ptr(), N, (int)H, (int)W, (int)C,
-                                   K, P, Q, (int)R, (int)S, (int)sy, (int)sx,
-                                   (int)py, (int)px, true, cur_stream(),
-                                   nullptr, skp.data_ptr<float>(), SK, cnt);
-            return dx;
-        }
         fda::conv_igemm_launch(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(),
                                N, (int)H, (int)W, (int)C, K, P, Q, (int)R,
                                (int)S, (int)sy, (int)sx, (int)py, (int)px,
-                               true, cur_stream(), nullptr,
+                               /*dgrad=*/true, cur_stream(), nullptr,
                                skp.data_ptr<float>(), SK);
         fda::conv_skcombine_launch(skp.data_ptr<float>(), dx.data_ptr(),
                                    nullptr, M, (int)C, SK,
@@ -557,84 +500,41 @@ at::Tensor conv_igemm_dgrad(at::Tensor dy, at::Tensor wt,
     fda::conv_igemm_launch(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(),
                            N, (int)H, (int)W, (int)C, K, P, Q, (int)R, (int)S,
                            (int)sy, (int)sx, (int)py, (int)px, /*dgrad=*/true,
-                           cur_stream(), nullptr, nullptr, 1, nullptr, accp);
+                           cur_stream(), nullptr, nullptr, 1, accp);
     return dx;
+}
+
+// wgrad: ws [K][R*S*C] fp32 (the channels_last weight-grad layout
+// [K][R][S][C] flattened), PRE-ZEROED, accumulated in place.
+// dy: [N,K,P,Q] channels_last bf16; x: [N,C,H,W] channels_last bf16.
+void conv_igemm_wgrad_into(at::Tensor dy, at::Tensor x, at::Tensor ws,
+                           int64_t R, int64_t S,
+                           int64_t sy, int64_t sx, int64_t py, int64_t px) {
+    // ws is typically a slice of the step-scoped wgrad arena (ops/conv.py),
+    // which saves the per-layer zeros launch.
+    TORCH_CHECK(dy.dim() == 4 && x.dim() == 4);
+    const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2),
+              W = (int)x.size(3);
+    const int K = (int)dy.size(1), P = (int)dy.size(2), Q = (int)dy.size(3);
+    check_conv_operands(dy, x, C, K);
+    TORCH_CHECK(ws.is_cuda() && ws.scalar_type() == at::kFloat &&
+                ws.is_contiguous());
+    TORCH_CHECK(ws.numel() == (int64_t)K * R * S * C);
+    fda::conv_wgrad_launch(dy.data_ptr(), x.data_ptr(), ws.data_ptr<float>(),
+                           N, H, W, C, K, P, Q, (int)R, (int)S, (int)sy,
+                           (int)sx, (int)py, (int)px, cur_stream());
 }
 
 at::Tensor conv_igemm_wgrad(at::Tensor dy, at::Tensor x,
                             int64_t R, int64_t S,
                             int64_t sy, int64_t sx, int64_t py, int64_t px) {
-    // dy: [N,K,P,Q] channels_last bf16; x: [N,C,H,W] channels_last bf16.
-    // Returns ws[K][R*S*C] fp32 (the channels_last weight-grad memory
-    // layout [K][R][S][C] flattened).
-    TORCH_CHECK(dy.is_cuda() && x.is_cuda());
-    TORCH_CHECK(dy.scalar_type() == at::kBFloat16 &&
-                x.scalar_type() == at::kBFloat16);
-    TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                x.is_contiguous(at::MemoryFormat::ChannelsLast));
-    const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2),
-              W = (int)x.size(3);
-    const int K = (int)dy.size(1), P = (int)dy.size(2), Q = (int)dy.size(3);
-    TORCH_CHECK(C % 64 == 0 && K % 64 == 0);
-    auto ws = at::zeros({K, R * S * C}, x.options().dtype(at::kFloat));
-    if (fda::conv_wgrad_two_phase()) {
-        int ft, mch, nch;
-        fda::conv_wgrad_plan((long)N * P * Q, C, K, (int)R, (int)S,
-                             &ft, &mch, &nch);
-        auto part = at::empty({(int64_t)nch, (int64_t)K * R * S * C},
-                              x.options().dtype(at::kFloat));
-        fda::conv_wgrad_launch(dy.data_ptr(), x.data_ptr(),
-                               ws.data_ptr<float>(), N, H, W, C, K, P, Q,
-                               (int)R, (int)S, (int)sy, (int)sx, (int)py,
-                               (int)px, cur_stream(),
-                               part.data_ptr<float>());
-        fda::wgrad_combine_launch(ws.data_ptr<float>(),
-                                  part.data_ptr<float>(),
-                                  (long)K * R * S * C, nch, cur_stream());
-        return ws;
-    }
-    fda::conv_wgrad_launch(dy.data_ptr(), x.data_ptr(), ws.data_ptr<float>(),
-                           N, H, W, C, K, P, Q, (int)R, (int)S, (int)sy,
-                           (int)sx, (int)py, (int)px, cur_stream());
+    TORCH_CHECK(dy.dim() == 4 && x.dim() == 4);
+    auto ws = at::zeros({dy.size(1), R * S * x.size(1)},
+                        x.options().dtype(at::kFloat));
+    conv_igemm_wgrad_into(dy, x, ws, R, S, sy, sx, py, px);
     return ws;
 }
 
-void conv_igemm_wgrad_into(at::Tensor dy, at::Tensor x, at::Tensor ws,
-                           int64_t R, int64_t S,
-                           int64_t sy, int64_t sx, int64_t py, int64_t px) {
-    // Accumulating variant: ws is a PRE-ZEROED [K, R*S*C] fp32 slice of the
-    // step-scoped wgrad arena (ops/conv.py) — saves the per-layer zeros
-    // launch.
-    TORCH_CHECK(dy.scalar_type() == at::kBFloat16 &&
-                x.scalar_type() == at::kBFloat16);
-    TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                x.is_contiguous(at::MemoryFormat::ChannelsLast));
-    TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous());
-    const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2),
-              W = (int)x.size(3);
-    const int K = (int)dy.size(1), P = (int)dy.size(2), Q = (int)dy.size(3);
-    TORCH_CHECK(C % 64 == 0 && K % 64 == 0);
-    TORCH_CHECK(ws.numel() == (int64_t)K * R * S * C);
-    if (fda::conv_wgrad_two_phase()) {
-        int ft, mch, nch;
-        fda::conv_wgrad_plan((long)N * P * Q, C, K, (int)R, (int)S,
-                             &ft, &mch, &nch);
-        auto part = at::empty({(int64_t)nch, (int64_t)K * R * S * C},
-                              x.options().dtype(at::kFloat));
-        fda::conv_wgrad_launch(dy.data_ptr(), x.data_ptr(),
-                               ws.data_ptr<float>(), N, H, W, C, K, P, Q,
-                               (int)R, (int)S, (int)sy, (int)sx, (int)py,
-                               (int)px, cur_stream(),
-                               part.data_ptr<float>());
-        fda::wgrad_combine_launch(ws.data_ptr<float>(),
-                                  part.data_ptr<float>(),
-                                  (long)K * R * S * C, nch, cur_stream());
-        return;
-    }
-    fda::conv_wgrad_launch(dy.data_ptr(), x.data_ptr(), ws.data_ptr<float>(),
-                           N, H, W, C, K, P, Q, (int)R, (int)S, (int)sy,
-                           (int)sx, (int)py, (int)px, cur_stream());
-}
 
 at::Tensor conv_stem_fwd(at::Tensor x8, at::Tensor wpad, int64_t R,
                          int64_t sy, int64_t sx, int64_t P, int64_t Q) {

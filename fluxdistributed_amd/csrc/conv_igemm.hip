@@ -1,7 +1,7 @@
 // Implicit-GEMM 2D convolution for gfx950 (CDNA4), NHWC bf16.
 //
 // MI355X-native replacement for the conv layer the reference gets for free
-// from cuDNN via NNlibCUDA (/root/reference -> Flux conv):
+// from cuDNN via NNlibCUDA (Flux conv):
 // hand-written MFMA kernels — v_mfma_f32_16x16x32_bf16 tiles, LDS staging
 // via global_load_lds (direct HBM->LDS DMA), source-side XOR swizzle for
 // bank-conflict-free ds_read_b128 fragment reads (guide T2 / rule 21),
@@ -27,6 +27,14 @@
 // MFMA-per-glds ratio is what sets throughput, guide §5 ladder):
 //   OC % 128 == 0 : BM=128 x BN=128, 4 waves as 2x2, LDS 2x32 KiB
 //   OC % 128 != 0 : BM=256 x BN=64,  4 waves as 4x1, LDS 2x40 KiB
+// Each tile has a second config for grids big enough to fill it: BK=32
+// K-steps on a 3-buffer counted ring (3x16 KiB at 3 blocks/CU, 3x20 KiB at
+// 2), chosen in conv_dispatch. Kernels in this file: conv_igemm_kernel
+// fwd+dgrad x 2 tiles x {BK64 2-buf, BK32 3-ring} (8) + the stem (1),
+// conv_wgrad_kernel FT2 / FT2-stem / FT4 (3), conv_skcombine_kernel,
+// wt_transpose_kernel. Variants that were measured and rejected are
+// recorded in profiles/ab_conv8.md, profiles/ab_bigtile.md and
+// docs/wgrad_study.md, not kept here.
 // fp32 accumulate, bf16 store. Staging source offsets advance
 // incrementally within a filter tap (full address math only on tap
 // changes). The fwd epilogue can also emit per-channel sum/sumsq
@@ -71,10 +79,8 @@ enum ConvMode { CONV_FWD = 0, CONV_DGRAD = 1, CONV_STEM = 2 };
 
 constexpr int BK = 64;
 
-// NW = waves per block = (BM/64)*(BN/64): 4 for the 128x128 / 256x64
-// configs (256 threads, 2 blocks/CU), 8 for the 256x128 big tile (512
-// threads, 1 block/CU — fewer glds per wave per K-step: 6 vs 8, same 32
-// MFMAs, so a higher MFMA:staging ratio on the deep-K layers).
+// NW = waves per block = (BM/64)*(BN/64): 4 for both the 128x128 and the
+// 256x64 config (256 threads, at least 2 blocks/CU).
 template <int MODE, int BM, int BN, int WN, int NBUF = 2, int BKT = BK>
 __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64,
                              512 / ((BM / 64) * (BN / 64) * 64))
@@ -90,15 +96,10 @@ void conv_igemm_kernel(
                                  BN reduce+finalize directly (the separate
                                  bn_stats read pass is skipped) */
     float* __restrict__ skpart, /* split-K: fp32 partial output
-                                 [SK][M][OC]; reduced either by the
-                                 separate combine kernel or in-launch by
-                                 the last-arriving slice (cnt != null).
-                                 Small-M late layers fill only ~30% of the
-                                 chip otherwise. */
+                                 [SK][M][OC], reduced by
+                                 conv_skcombine_kernel. Small-M late layers
+                                 fill only ~30% of the chip otherwise. */
     int SK,
-    unsigned* __restrict__ cnt, /* in-launch combine tickets, one per
-                                 (m,n,zclass) tile, memset to 0 before the
-                                 launch; null = separate combine kernel */
     const unsigned short* __restrict__ accsrc
         /* non-null (dgrad): bf16 tensor with the OUTPUT's layout added into
            the result before the store — the residual-junction grad
@@ -307,16 +308,12 @@ void conv_igemm_kernel(
         // reading before it arrived here. With NBUF==3 the counted wait
         // leaves tile it+1's DMA in flight across the barrier (T4).
         if (NBUF > 2 && it + 1 < itN) {
+            static_assert(NBUF == 2 || GPW == 4 || GPW == 5,
+                          "counted ring: state the vmcnt for this GPW");
             if constexpr (GPW == 4)
                 asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else if constexpr (GPW == 5)
-                asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-            else if constexpr (GPW == 6)
-                asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            else if constexpr (GPW == 8)
-                asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             else
-                asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
+                asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -402,70 +399,6 @@ void conv_igemm_kernel(
             }
         }
     }
-    if (skpart != nullptr && cnt != nullptr) {
-        // ---- in-launch split-K seam (guide §6 Guideline 16, counter form):
-        // publish this slice's fp32 slab with an agent-scope release and
-        // take a ticket; the last-arriving slice re-reads all SK slabs,
-        // writes the bf16 tile and accumulates the BN stats partials.
-        // Saves the separate combine kernel's launch boundary + the slab
-        // round trip on shallow-K small-M shapes, which is why split-K can
-        // trigger there at all (the round-trip combine measured a net loss
-        // below T=48).
-        const long tileid =
-            ((long)zrest * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        unsigned* flag = (unsigned*)lds;      // reuse the ONE shared array
-        if (threadIdx.x == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            // restated wait: ROCm 7.2 drops the post-wbl2 vmcnt when its
-            // scoreboard says this wave has nothing outstanding
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const unsigned t = __hip_atomic_fetch_add(
-                &cnt[tileid], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            flag[0] = (t == (unsigned)SK - 1) ? 1u : 0u;
-        }
-        __syncthreads();
-        const bool im_last = flag[0] != 0;
-        __syncthreads();          // flag consumed before any lds reuse
-        if (!im_last) return;
-        if (threadIdx.x == 0)
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        __syncthreads();
-        #pragma unroll
-        for (int mi = 0; mi < 4; ++mi) {
-            #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const long m = m0 + wm * 64 + mi * 16 + frow0 + j;
-                if (m >= M) continue;
-                long obase;
-                if (MODE != CONV_DGRAD) {
-                    obase = m * OC;
-                } else {
-                    const int ww = (int)(m % OW);
-                    const int hh = (int)((m / OW) % OH);
-                    const int n = (int)(m / ((long)OW * OH));
-                    obase = (((long)n * H + a + (long)sy * hh) * W + b +
-                             (long)sx * ww) * C;
-                }
-                const float* prow = skpart + m * OC + n0 + wn * 64;
-                unsigned short* orow = out + obase + n0 + wn * 64;
-                #pragma unroll
-                for (int ni = 0; ni < 4; ++ni) {
-                    float v = 0.f;
-                    for (int z = 0; z < SK; ++z)
-                        v += prow[(long)z * M * OC + ni * 16 + fcol];
-                    const unsigned short us = f32_to_bf16bits(v);
-                    orow[ni * 16 + fcol] = us;
-                    if (MODE != CONV_DGRAD && stats != nullptr) {
-                        const float vr = bf16bits_to_f32(us);
-                        ssum[ni] += vr;
-                        sq[ni] += vr * vr;
-                    }
-                }
-            }
-        }
-    }
 
     if (MODE != CONV_DGRAD && stats != nullptr) {
         // fold the four 16-row lane groups, then the waves sharing this
@@ -510,7 +443,6 @@ static void launch_cfg(const void* src, const void* wgt, void* out,
                        int R, int S, int sy, int sx, int py, int px,
                        hipStream_t stream, float* stats = nullptr,
                        float* skpart = nullptr, int SK = 1,
-                       unsigned* cnt = nullptr,
                        const void* accsrc = nullptr) {
     const int OC = (MODE == CONV_DGRAD) ? C : K;
     const long M = (MODE != CONV_DGRAD)
@@ -535,7 +467,7 @@ static void launch_cfg(const void* src, const void* wgt, void* out,
                        (const unsigned short*)src,
                        (const unsigned short*)wgt, (unsigned short*)out,
                        N, H, W, C, K, P, Q, R, S, sy, sx, py, px, stats,
-                       skpart, SK, cnt, (const unsigned short*)accsrc);
+                       skpart, SK, (const unsigned short*)accsrc);
 }
 
 // ---- split-K combine: y = bf16(sum_sk part) (+ BN stats partials) --------
@@ -623,360 +555,6 @@ void conv_skcombine_launch(const float* part, void* y, float* stats, long M,
                        (const unsigned short*)accsrc);
 }
 
-
-// ---- 8-phase fine-interleave variant (guide §5 "256² 8-phase template",
-// adapted to the conv gather): 256x128 tile, 8 waves (4M x 2N), 512
-// threads, 1 block/CU, 3 LDS buffers (144 KiB). Each K-step runs as 4
-// phases of [ds-read subtile | stage chunk of tile t+2 | raw barrier |
-// lgkmcnt(0) | 8 MFMAs | raw barrier]; the tile drain is ONE counted
-// s_waitcnt vmcnt(12) per K-step (2 newer tiles x 6 glds/wave stay in
-// flight), so DMA latency spans ~4-8 phases of MFMA work instead of
-// stalling at a single per-step barrier. FLUXDIST_CONV8 gates dispatch.
-template <int MODE>
-__global__ __launch_bounds__(512, 1) void conv_igemm8_kernel(
-    const unsigned short* __restrict__ src,
-    const unsigned short* __restrict__ wgt,
-    unsigned short* __restrict__ out,
-    int N, int H, int W, int C,
-    int K, int P, int Q,
-    int R, int S, int sy, int sx, int py, int px,
-    float* __restrict__ stats,
-    const unsigned short* __restrict__ accsrc) {
-    constexpr int BM = 256, BN = 128, NBUF = 3;
-    constexpr int BKT = BK;              // this variant is BK=64 only
-    constexpr int RPG = 8, GPR = 8;      // rows / 16-B granules per glds
-    constexpr int KH = 2;                // mfma k-halves (BK=64)
-    auto swz = [](int row) { return row & 7; };
-    constexpr int A_ELEMS = BM * BKT;
-    constexpr int B_ELEMS = BN * BKT;
-    constexpr int BUF_ELEMS = A_ELEMS + B_ELEMS;
-    constexpr int AI = 4, BI = 2;        // glds per wave per tile
-    constexpr int NW = 8, WN = 2;
-
-    const int OC = (MODE == CONV_DGRAD) ? C : K;
-    const int RC = (MODE == CONV_FWD) ? C : K;
-
-    int a = 0, b = 0, OH, OW, r0 = 0, s0 = 0, nR = R, nS = S;
-    if (MODE != CONV_DGRAD) {
-        OH = P; OW = Q;
-    } else {
-        a = blockIdx.z / sx;  b = blockIdx.z % sx;
-        OH = (H - a + sy - 1) / sy;
-        OW = (W - b + sx - 1) / sx;
-        r0 = (a + py) % sy;  nR = (R - r0 + sy - 1) / sy;
-        s0 = (b + px) % sx;  nS = (S - s0 + sx - 1) / sx;
-        if (OH <= 0 || OW <= 0) return;
-        if (nR < 0) nR = 0;
-        if (nS < 0) nS = 0;
-    }
-    const long M = (long)N * OH * OW;
-    const long m0 = (long)blockIdx.x * BM;
-    if (m0 >= M) return;
-    const int n0 = blockIdx.y * BN;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = tid >> 6;
-    const int wm = wid >> 1;
-    const int wn = wid & 1;
-
-    extern __shared__ unsigned short lds[];   // [NBUF][BUF_ELEMS]
-
-    // ---- per-lane staging descriptors (same gather as conv_igemm_kernel)
-    int a_row[AI];
-    long a_pix[AI];
-    int a_hb[AI], a_wb[AI];
-    bool a_mok[AI];
-    const int cslot = lane % GPR;
-    #pragma unroll
-    for (int i = 0; i < AI; ++i) {
-        const int row = (wid * AI + i) * RPG + lane / GPR;
-        a_row[i] = row;
-        const long m = m0 + row;
-        const bool mok = m < M;
-        const long mm = mok ? m : 0;
-        const int ow = (int)(mm % OW);
-        const int oh = (int)((mm / OW) % OH);
-        const int n = (int)(mm / ((long)OW * OH));
-        a_mok[i] = mok;
-        if (MODE == CONV_FWD) {
-            a_hb[i] = oh * sy - py;
-            a_wb[i] = ow * sx - px;
-            a_pix[i] = ((long)n * H) * W * C;
-        } else {
-            a_hb[i] = oh + (a + py) / sy;
-            a_wb[i] = ow + (b + px) / sx;
-            a_pix[i] = ((long)n * P) * Q * K;
-        }
-    }
-    int b_row[BI];
-    #pragma unroll
-    for (int i = 0; i < BI; ++i)
-        b_row[i] = (wid * BI + i) * RPG + lane / GPR;
-
-    const int cblocks = RC / BKT;
-    const int T = nR * nS * cblocks;
-
-    long a_goff[AI];
-    bool a_okc[AI];
-    long b_goff[BI];
-    int last_rsi = -1;
-    auto advance = [&](int it) {
-        const int rsi = it / cblocks;
-        const int ri = rsi / nS, si = rsi % nS;
-        if (rsi != last_rsi) {
-            last_rsi = rsi;
-            const int cb = (it % cblocks) * BK;
-            #pragma unroll
-            for (int i = 0; i < AI; ++i) {
-                bool ok = a_mok[i];
-                long off = 0;
-                if (MODE == CONV_FWD) {
-                    const int h = a_hb[i] + ri, w = a_wb[i] + si;
-                    ok = ok && (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
-                    off = a_pix[i] + ((long)h * W + w) * C + cb + (cslot ^ (a_row[i] & 7)) * 8;
-                } else {
-                    const int pp = a_hb[i] - ri, qq = a_wb[i] - si;
-                    ok = ok && (unsigned)pp < (unsigned)P && (unsigned)qq < (unsigned)Q;
-                    off = a_pix[i] + ((long)pp * Q + qq) * K + cb + (cslot ^ (a_row[i] & 7)) * 8;
-                }
-                a_goff[i] = off;
-                a_okc[i] = ok;
-            }
-            const int r = r0 + ri * ((MODE == CONV_FWD) ? 1 : sy);
-            const int sss = s0 + si * ((MODE == CONV_FWD) ? 1 : sx);
-            const int rs = r * S + sss;
-            #pragma unroll
-            for (int i = 0; i < BI; ++i) {
-                const int row = b_row[i];
-                const int cs = (cslot ^ (row & (GPR - 1))) * 8;
-                if (MODE == CONV_FWD)
-                    b_goff[i] = (long)(n0 + row) * R * S * C + (long)rs * C + cb + cs;
-                else
-                    b_goff[i] = (long)((long)rs * C + n0 + row) * K + cb + cs;
-            }
-        } else {
-            #pragma unroll
-            for (int i = 0; i < AI; ++i) a_goff[i] += BK;
-            #pragma unroll
-            for (int i = 0; i < BI; ++i) b_goff[i] += BK;
-        }
-    };
-
-    // fragment read offsets
-    int a_off[4][KH], b_off[4][KH];
-    {
-        const int fr = lane & 15, fq = lane >> 4;
-        #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-            #pragma unroll
-            for (int kh = 0; kh < KH; ++kh) {
-                const int row = wm * 64 + mi * 16 + fr;
-                const int slot = ((kh * 4 + fq) ^ swz(row)) & (GPR - 1);
-                a_off[mi][kh] = row * BKT + slot * 8;
-            }
-        #pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-            #pragma unroll
-            for (int kh = 0; kh < KH; ++kh) {
-                const int row = wn * 64 + ni * 16 + fr;
-                const int slot = ((kh * 4 + fq) ^ swz(row)) & (GPR - 1);
-                b_off[ni][kh] = A_ELEMS + row * BKT + slot * 8;
-            }
-    }
-
-    floatx4 acc[4][4];
-    #pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-        #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = floatx4{0.f, 0.f, 0.f, 0.f};
-
-    auto issueA = [&](int buf, int i) {
-        unsigned short* base = lds + buf * BUF_ELEMS;
-        const unsigned short* sp = a_okc[i] ? src + a_goff[i] : conv_zero16;
-        FDA_GLDS16(sp, base + (wid * AI + i) * 8 * BK);
-    };
-    auto issueB = [&](int buf, int i) {
-        unsigned short* base = lds + buf * BUF_ELEMS;
-        FDA_GLDS16(wgt + b_goff[i], base + A_ELEMS + (wid * BI + i) * 8 * BK);
-    };
-    auto stage_all = [&](int buf, int it) {   // prologue only
-        advance(it);
-        #pragma unroll
-        for (int i = 0; i < AI; ++i) issueA(buf, i);
-        #pragma unroll
-        for (int i = 0; i < BI; ++i) issueB(buf, i);
-    };
-
-    if (T > 0) stage_all(0, 0);
-    if (T > 1) stage_all(1, 1);
-
-    for (int it = 0; it < T; ++it) {
-        const int buf = it % NBUF;
-        const unsigned short* rbuf = lds + buf * BUF_ELEMS;
-        const int sbuf = (it + 2) % NBUF;
-        const bool do_stage = it + 2 < T;
-        if (do_stage) advance(it + 2);
-        // drain THIS tile's 6 glds; leave the 2 newer tiles (<=12) in flight
-        if (it + 1 < T)
-            asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        else
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-
-        short8 af0[4], af1[4], bf[4][2];
-        // ---- phase 0: kh=0 (16 MFMAs) ----------------------------------
-        // 2 phases of 16 MFMAs: the 4x8-MFMA grain measured ~10% SLOWER
-        // (per-phase barrier cost not amortized at this tile size;
-        // profiles/ab_conv8.md).
-        #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-            af0[mi] = *(const short8*)(rbuf + a_off[mi][0]);
-        #pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-            bf[ni][0] = *(const short8*)(rbuf + b_off[ni][0]);
-        if (do_stage) { issueA(sbuf, 0); issueA(sbuf, 1); issueA(sbuf, 2); }
-        __builtin_amdgcn_s_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_setprio(1);
-        #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-            #pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-                acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                    af0[mi], bf[ni][0], acc[mi][ni], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_s_barrier();
-        // ---- phase 1: kh=1 (16 MFMAs) ----------------------------------
-        #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-            af1[mi] = *(const short8*)(rbuf + a_off[mi][1]);
-        #pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-            bf[ni][1] = *(const short8*)(rbuf + b_off[ni][1]);
-        if (do_stage) { issueA(sbuf, 3); issueB(sbuf, 0); issueB(sbuf, 1); }
-        __builtin_amdgcn_s_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_setprio(1);
-        #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-            #pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-                acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                    af1[mi], bf[ni][1], acc[mi][ni], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_s_barrier();
-    }
-
-    // ---- epilogue (same mapping as conv_igemm_kernel) --------------------
-    const int fcol = lane & 15, frow0 = (lane >> 4) * 4;
-    float ssum[4] = {0.f, 0.f, 0.f, 0.f};
-    float sq[4] = {0.f, 0.f, 0.f, 0.f};
-    #pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
-        #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const long m = m0 + wm * 64 + mi * 16 + frow0 + j;
-            if (m >= M) continue;
-            long obase;
-            if (MODE != CONV_DGRAD) {
-                obase = m * OC;
-            } else {
-                const int ww = (int)(m % OW);
-                const int hh = (int)((m / OW) % OH);
-                const int n = (int)(m / ((long)OW * OH));
-                obase = (((long)n * H + a + (long)sy * hh) * W + b +
-                         (long)sx * ww) * C;
-            }
-            unsigned short* orow = out + obase + n0 + wn * 64;
-            const unsigned short* arow =
-                accsrc ? accsrc + obase + n0 + wn * 64 : nullptr;
-            #pragma unroll
-            for (int ni = 0; ni < 4; ++ni) {
-                float v = acc[mi][ni][j];
-                if (arow) v += bf16bits_to_f32(arow[ni * 16 + fcol]);
-                const unsigned short us = f32_to_bf16bits(v);
-                orow[ni * 16 + fcol] = us;
-                if (MODE != CONV_DGRAD && stats != nullptr) {
-                    const float vr = bf16bits_to_f32(us);
-                    ssum[ni] += vr;
-                    sq[ni] += vr * vr;
-                }
-            }
-        }
-    }
-    if (MODE != CONV_DGRAD && stats != nullptr) {
-        #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-            #pragma unroll
-            for (int off = 16; off < 64; off <<= 1) {
-                ssum[ni] += __shfl_xor(ssum[ni], off, 64);
-                sq[ni] += __shfl_xor(sq[ni], off, 64);
-            }
-        }
-        float* sf = (float*)lds;
-        __builtin_amdgcn_s_barrier();
-        if ((lane >> 4) == 0) {
-            #pragma unroll
-            for (int ni = 0; ni < 4; ++ni) {
-                sf[(wid * 4 + ni) * 16 + fcol] = ssum[ni];
-                sf[NW * 64 + (wid * 4 + ni) * 16 + fcol] = sq[ni];
-            }
-        }
-        __builtin_amdgcn_s_barrier();
-        if (wm == 0 && (lane >> 4) == 0) {
-            float* prow = stats + (long)blockIdx.x * 2 * OC + n0 + wn * 64;
-            #pragma unroll
-            for (int ni = 0; ni < 4; ++ni) {
-                float s2 = ssum[ni], z = sq[ni];
-                for (int w2 = wid + WN; w2 < NW; w2 += WN) {
-                    s2 += sf[(w2 * 4 + ni) * 16 + fcol];
-                    z += sf[NW * 64 + (w2 * 4 + ni) * 16 + fcol];
-                }
-                prow[ni * 16 + fcol] = s2;
-                prow[OC + ni * 16 + fcol] = z;
-            }
-        }
-    }
-}
-
-int conv8_enabled() {
-    // 8-phase variant A/B knob: FLUXDIST_CONV8=1 routes eligible shapes
-    // (OC%128, SK==1, grid fills at 1 block/CU) through conv_igemm8_kernel.
-    static int v = [] {
-        const char* e = getenv("FLUXDIST_CONV8");
-        return e ? atoi(e) : 0;
-    }();
-    return v;
-}
-
-template <int MODE>
-static void launch_cfg8(const void* src, const void* wgt, void* out,
-                        int N, int H, int W, int C, int K, int P, int Q,
-                        int R, int S, int sy, int sx, int py, int px,
-                        hipStream_t stream, float* stats,
-                        const void* accsrc) {
-    const int OC = (MODE == CONV_DGRAD) ? C : K;
-    const long M = (MODE != CONV_DGRAD)
-        ? (long)N * P * Q
-        : (long)N * ((H + sy - 1) / sy) * ((W + sx - 1) / sx);
-    const unsigned zbase = (MODE != CONV_DGRAD) ? 1u : (unsigned)(sy * sx);
-    dim3 grid((unsigned)((M + 255) / 256), (unsigned)(OC / 128), zbase);
-    const size_t shmem = 3 * (256 * BK + 128 * BK) * sizeof(unsigned short);
-    static bool raised = [] {
-        hipFuncSetAttribute((const void*)&conv_igemm8_kernel<MODE>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024);
-        return true;
-    }();
-    (void)raised;
-    hipLaunchKernelGGL((conv_igemm8_kernel<MODE>), grid, dim3(512), shmem,
-                       stream, (const unsigned short*)src,
-                       (const unsigned short*)wgt, (unsigned short*)out,
-                       N, H, W, C, K, P, Q, R, S, sy, sx, py, px, stats,
-                       (const unsigned short*)accsrc);
-}
-
 void conv_stem_fwd_launch(const void* src, const void* wgt, void* out,
                           int N, int Hp, int Wp, int K, int P, int Q,
                           int R, int sy, int sx, hipStream_t stream,
@@ -988,232 +566,105 @@ void conv_stem_fwd_launch(const void* src, const void* wgt, void* out,
                                       stats);
 }
 
-static int conv_nbuf() {
-    // A/B knob: FLUXDIST_CONV_NBUF=3 -> 3-buffer counted ring (1 block/CU
-    // for the 128x128 config; 96 KiB LDS) vs default 2 (2 blocks/CU).
-    static int v = [] {
-        const char* e = getenv("FLUXDIST_CONV_NBUF");
-        return (e && e[0] == '3') ? 3 : 2;
-    }();
-    return v;
-}
-
-int conv_bk32_knob() {
-    // BK=32 x NBUF=3 for the 128x128 config: 48 KB LDS/block -> 3
-    // blocks/CU (12 waves) vs the default's 2. Measured (r2 A/B,
-    // profiles/ab_conv8.md addendum): -9..-28% on the big-M layer-1/2
-    // legs, +17% on the small-M 14x14 legs (294 blocks can't feed 3
-    // blocks/CU), so dispatch is grid-size-gated below. 0 = never,
-    // 1 = gated by fill (default), 2 = force everywhere (A/B).
-    static int v = [] {
+static bool conv_bk32() {
+    // BK=32 x NBUF=3 rings (FLUXDIST_CONV_BK32, 0 = off, default 1 = on,
+    // gated by grid fill in conv_dispatch). 128x128: 48 KB LDS/block -> 3
+    // blocks/CU (12 waves) vs the BK64 default's 2; measured -9..-28% on
+    // the big-M layer-1/2 legs, +17% on the small-M 14x14 legs (294 blocks
+    // can't feed 3 blocks/CU — profiles/ab_conv8.md addendum), hence the
+    // gate. 256x64: same 2 blocks/CU and 3.2:1 MFMA:glds ratio as BK64, but
+    // with a second tile in flight (2 x 60 KB fits; 3 x 80 KB at BK64 never
+    // did).
+    static const bool v = [] {
         const char* e = getenv("FLUXDIST_CONV_BK32");
-        return e ? atoi(e) : 1;
+        return e ? atoi(e) != 0 : true;
     }();
     return v;
 }
 
-int conv_bk32_check(long blocks64);
-
-int conv_bk32_check(long blocks64) {
-    // 128x64 x BK32 gate — measured a large LOSS on layer 1 (fwd 61->99,
-    // dgrad 76->100 us: the 2-wave block drops the MFMA:glds ratio to
-    // 2.7:1 and these legs are staging-bandwidth-bound). Only the forced
-    // A/B mode (FLUXDIST_CONV_BK32=2) takes it; the 128x128 BK32 config
-    // keeps its own fill gate (the measured +3.8% win).
-    extern int conv_bk32_knob();
-    (void)blocks64;
-    return conv_bk32_knob() >= 2;
-}
-
-static int conv_bigtile() {
-    // 256x128 512-thread tile (8 waves, 6 glds/wave/K-step at the same 32
-    // MFMAs). A/B knob FLUXDIST_CONV_BIGTILE: 0 = never, 1 = whenever
-    // OC%128==0 and the grid still fills at 1 block/CU. Default 0: the r2
-    // microbench measured it 3-13% SLOWER on every eligible leg (block-
-    // level overlap lost at 1 block/CU — same mechanism as NBUF=3,
-    // profiles/ab_bigtile.md).
-    static int v = [] {
-        const char* e = getenv("FLUXDIST_CONV_BIGTILE");
-        return e ? atoi(e) : 0;
-    }();
-    return v;
-}
-
-int conv8_enabled();   // defined below (8-phase variant knob)
-
-bool conv_use_inlsk() {
-    // in-launch split-K combine (last-arriver seam) vs the separate
-    // combine kernel. Default OFF: measured 2-2.6x SLOWER than the
-    // round-trip combine on every SK shape (r2 A/B, profiles/ab_inlsk.md)
-    // — the per-block agent-release fence (buffer_wbl2 L2 writeback) and
-    // the reducer's serial slab re-read dwarf the saved launch boundary at
-    // these 64 KB/tile slab sizes. Kept behind FLUXDIST_CONV_INLSK=1 for
-    // future shapes with small slabs.
-    static bool v = [] {
-        const char* e = getenv("FLUXDIST_CONV_INLSK");
-        return e && e[0] == '1';
-    }();
-    return v;
+// tile geometry: a function of the output channel count alone
+static void conv_tile(int OC, int* bm, int* bn) {
+    const bool big = OC % 128 == 0;
+    *bm = big ? 128 : 256;
+    *bn = big ? 128 : 64;
 }
 
 // One place that decides tile geometry + split-K for a conv launch; the
-// torch bindings call this too so the stats/skpart workspace shapes always
-// match what the kernel will write.
+// torch bindings call this so the stats/skpart workspace shapes always
+// match what the kernel will write (the launcher takes BM/BN from the same
+// conv_tile and SK from its caller).
 //   M   = output rows (per z-class for dgrad), OC = output channels,
 //   T   = K-loop depth in BK=64 steps (nR*nS*RC/64), zbase = sy*sx classes
 //         for strided dgrad else 1.
 // split-K only when the launch would underfill the 256-CU chip AND the
 // K-loop is deep enough to amortize the fp32 partial round-trip (T < 48
 // measured a net loss: 14x14 / 1x1 shapes regressed up to 3x on a blanket
-// trigger).
+// trigger — the 4-6x slab traffic dominates at shallow T, those legs are
+// traffic-bound, not fill-bound).
 void conv_igemm_plan(long M, int OC, long T, int zbase,
                      int* bm, int* bn, int* sk) {
-    const bool big = OC % 128 == 0;
-    int BM = big ? 128 : 256;
-    int BN = big ? 128 : 64;
-    int SK = 1;
-    // T >= 48 only: shallow-K shapes measured a net loss under split-K on
-    // BOTH combine flavors (round-trip r1.14; in-launch seam r2 A/B — the
-    // 4-6x slab traffic dominates at shallow T, these legs are
-    // traffic-bound, not fill-bound).
+    conv_tile(OC, bm, bn);
+    *sk = 1;
     if (T >= 48) {
-        const long blocks = ((M + BM - 1) / BM) * (OC / BN) * zbase;
-        if (blocks < 192) SK = 4;
-        else if (blocks < 384) SK = 2;
+        const long blocks = ((M + *bm - 1) / *bm) * (OC / *bn) * zbase;
+        if (blocks < 192) *sk = 4;
+        else if (blocks < 384) *sk = 2;
     }
-    if (big && SK == 1 && (conv_bigtile() || conv8_enabled())) {
-        const long blocks256 = ((M + 255) / 256) * (OC / 128) * zbase;
-        if (blocks256 >= 256) { BM = 256; BN = 128; }
+}
+
+template <int MODE>
+static void conv_dispatch(const void* src, const void* wgt, void* out,
+                          int N, int H, int W, int C, int K, int P, int Q,
+                          int R, int S, int sy, int sx, int py, int px,
+                          hipStream_t stream, float* stats, float* skpart,
+                          int SK, const void* accsrc) {
+    constexpr bool dgrad = MODE == CONV_DGRAD;
+    const int OC = dgrad ? C : K;
+    const long Mv = !dgrad
+        ? (long)N * P * Q
+        : (long)N * ((H + sy - 1) / sy) * ((W + sx - 1) / sx);
+    const long zbase = dgrad ? sy * sx : 1;
+    int BM, BN;
+    conv_tile(OC, &BM, &BN);
+    const long blocks = ((Mv + BM - 1) / BM) * (OC / BN) * zbase * SK;
+    // the BK32 rings need the grid to fill their blocks/CU: >= ~576 blocks
+    // at 3 blocks/CU (128x128), >= 512 at 2 (256x64); below that the lost
+    // per-block depth outweighs the extra overlap
+    if (BN == 128) {
+        if (conv_bk32() && blocks >= 576)
+            launch_cfg<MODE, 128, 128, 2, 3, 32>(
+                src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
+                stream, stats, skpart, SK, accsrc);
+        else
+            launch_cfg<MODE, 128, 128, 2>(
+                src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
+                stream, stats, skpart, SK, accsrc);
+    } else {
+        if (conv_bk32() && blocks >= 512)
+            launch_cfg<MODE, 256, 64, 1, 3, 32>(
+                src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
+                stream, stats, skpart, SK, accsrc);
+        else
+            launch_cfg<MODE, 256, 64, 1>(
+                src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
+                stream, stats, skpart, SK, accsrc);
     }
-    if (!big) {
-        // 64-channel shapes may take the 128x64 x BK32 config (4 blocks/
-        // CU); BM=128 here so the stats workspace matches the launch
-        const long blocks64 = ((M + 127) / 128) * (OC / 64) * zbase * SK;
-        extern int conv_bk32_check(long blocks64);
-        if (conv_bk32_check(blocks64)) BM = 128;
-    }
-    *bm = BM; *bn = BN; *sk = SK;
 }
 
 void conv_igemm_launch(const void* src, const void* wgt, void* out,
                        int N, int H, int W, int C, int K, int P, int Q,
                        int R, int S, int sy, int sx, int py, int px,
                        bool dgrad, hipStream_t stream, float* stats,
-                       float* skpart, int SK, unsigned* cnt,
-                       const void* accsrc) {
-    const int OC = dgrad ? C : K;
-    const bool nb3 = conv_nbuf() == 3;
-    const long Mv = !dgrad
-        ? (long)N * P * Q
-        : (long)N * ((H + sy - 1) / sy) * ((W + sx - 1) / sx);
-    const int zbase = dgrad ? sy * sx : 1;
-    const long RC = dgrad ? K : C;
-    // T here mirrors the bindings' SK trigger; the plan's BM/BN choice is
-    // what this function must obey so workspace shapes match
-    int BM, BN, SKp;
-    conv_igemm_plan(Mv, OC, (long)R * S * (RC / 64), zbase, &BM, &BN, &SKp);
-    const bool big = BN == 128;
-    if (BM == 256 && BN == 128) {
-        if (conv8_enabled()) {     // 8-phase fine-interleave variant
-            if (dgrad)
-                launch_cfg8<CONV_DGRAD>(src, wgt, out, N, H, W, C, K, P, Q,
-                                        R, S, sy, sx, py, px, stream,
-                                        nullptr, accsrc);
-            else
-                launch_cfg8<CONV_FWD>(src, wgt, out, N, H, W, C, K, P, Q,
-                                      R, S, sy, sx, py, px, stream, stats,
-                                      accsrc);
-            return;
-        }
-        if (dgrad)
-            launch_cfg<CONV_DGRAD, 256, 128, 2, 2>(
-                src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
-                stream, nullptr, skpart, SK, cnt, accsrc);
-        else
-            launch_cfg<CONV_FWD, 256, 128, 2, 2>(
-                src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
-                stream, stats, skpart, SK, cnt, accsrc);
-        return;
-    }
-    // the 3-blocks/CU BK32 config needs >=~576 blocks to fill; below
-    // that the lost per-block depth outweighs the extra block overlap
-    const long blocks128 =
-        ((Mv + 127) / 128) * (OC / 128) * (long)zbase * SK;
-    const bool bk32 = big && conv_bk32_knob() &&
-                      (conv_bk32_knob() >= 2 || blocks128 >= 576);
-    // 64-channel shapes (layer 1): 128x64 x BK32 x NBUF3 = 36 KB LDS ->
-    // 4 blocks/CU of 2 waves; the plan already switched BM to 128 when
-    // the grid qualifies (stats workspace sizing must match)
-    const bool bk32s = !big && BM == 128;
-    // 256x64 x BK32 x 3-ring: SAME 2 blocks/CU and the same 3.2:1
-    // MFMA:glds ratio as the BK64 default, but with a second tile in
-    // flight (60 KB x 2 fits; 3 x 80 KB at BK64 never did)
-    const long blocks256x64 =
-        ((Mv + 255) / 256) * (OC / 64) * (long)zbase * SK;
-    const bool bk32r = !big && BM == 256 && conv_bk32_knob() &&
-                       (conv_bk32_knob() >= 2 || blocks256x64 >= 512);
-    if (dgrad) {
-        if (bk32)
-            launch_cfg<CONV_DGRAD, 128, 128, 2, 3, 32>(
-                src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
-                stream, nullptr, skpart, SK, cnt, accsrc);
-        else if (big && nb3)
-            launch_cfg<CONV_DGRAD, 128, 128, 2, 3>(src, wgt, out, N, H, W, C,
-                                                   K, P, Q, R, S, sy, sx, py,
-                                                   px, stream, nullptr,
-                                                   skpart, SK, cnt, accsrc);
-        else if (big)
-            launch_cfg<CONV_DGRAD, 128, 128, 2>(src, wgt, out, N, H, W, C, K,
-                                                P, Q, R, S, sy, sx, py, px,
-                                                stream, nullptr, skpart, SK,
-                                                cnt, accsrc);
-        else if (bk32s)
-            launch_cfg<CONV_DGRAD, 128, 64, 1, 3, 32>(
-                src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
-                stream, nullptr, skpart, SK, cnt, accsrc);
-        else if (bk32r)
-            launch_cfg<CONV_DGRAD, 256, 64, 1, 3, 32>(
-                src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
-                stream, nullptr, skpart, SK, cnt, accsrc);
-        else
-            launch_cfg<CONV_DGRAD, 256, 64, 1>(src, wgt, out, N, H, W, C, K,
-                                               P, Q, R, S, sy, sx, py, px,
-                                               stream, nullptr, skpart, SK,
-                                               cnt, accsrc);
-    } else {
-        if (bk32)
-            launch_cfg<CONV_FWD, 128, 128, 2, 3, 32>(
-                src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
-                stream, stats, skpart, SK, cnt, accsrc);
-        else if (big && nb3)
-            launch_cfg<CONV_FWD, 128, 128, 2, 3>(src, wgt, out, N, H, W, C,
-                                                 K, P, Q, R, S, sy, sx, py,
-                                                 px, stream, stats, skpart,
-                                                 SK, cnt);
-        else if (big)
-            launch_cfg<CONV_FWD, 128, 128, 2>(src, wgt, out, N, H, W, C, K,
-                                              P, Q, R, S, sy, sx, py, px,
-                                              stream, stats, skpart, SK,
-                                              cnt);
-        else if (bk32s)
-            launch_cfg<CONV_FWD, 128, 64, 1, 3, 32>(
-                src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
-                stream, stats, skpart, SK, cnt, accsrc);
-        else if (bk32r)
-            launch_cfg<CONV_FWD, 256, 64, 1, 3, 32>(
-                src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
-                stream, stats, skpart, SK, cnt, accsrc);
-        else
-            launch_cfg<CONV_FWD, 256, 64, 1>(src, wgt, out, N, H, W, C, K,
-                                             P, Q, R, S, sy, sx, py, px,
-                                             stream, stats, skpart, SK,
-                                             cnt);
-    }
+                       float* skpart, int SK, const void* accsrc) {
+    if (dgrad)
+        conv_dispatch<CONV_DGRAD>(src, wgt, out, N, H, W, C, K, P, Q, R, S,
+                                  sy, sx, py, px, stream, stats, skpart, SK,
+                                  accsrc);
+    else
+        conv_dispatch<CONV_FWD>(src, wgt, out, N, H, W, C, K, P, Q, R, S,
+                                sy, sx, py, px, stream, stats, skpart, SK,
+                                accsrc);
 }
-
-}  // namespace fda
-
-namespace fda {
 
 // ---- batched conv-weight transpose ----------------------------------------
 // One launch transposes every conv weight w[k][rs*C+c] -> wt[rs*C+c][k] for
@@ -1267,10 +718,6 @@ void wt_transpose_launch(const long* src_ptrs, long* dst_ptrs, const int* Ks,
                        src_ptrs, dst_ptrs, Ks, RCs, tile_counts);
 }
 
-}  // namespace fda
-
-namespace fda {
-
 typedef __attribute__((ext_vector_type(4))) short short4_;
 
 // ---- wgrad: dw[k][rs][c] = sum_m dy[m][k] * x_gather[m][c] ----------------
@@ -1291,21 +738,15 @@ typedef __attribute__((ext_vector_type(4))) short short4_;
 constexpr int WG_BM = 64;      // m per K-step
 constexpr int WG_MCH = 2048;   // pixels per block (chunk)
 
-template <int FT, bool STEM = false, bool ASMRD = false, int MB = WG_BM,
-          bool TP = false>
+template <int FT, bool STEM = false>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(
     const unsigned short* __restrict__ dy,   // [M][K] (NHWC out grad)
     const unsigned short* __restrict__ x,    // [N,H,W,C]
-    float* __restrict__ ws,  /* TP=false: [K][RS*C] fp32, pre-zeroed,
-                                accumulated with atomicAdd across chunks.
-                                TP=true (two-phase): [nch][K][RS*C] fp32
-                                partial slab, uninitialized — every chunk
-                                block plain-stores its full tile (PMC
-                                showed 100% of the atomics go to DRAM as
-                                serialized RMWs, docs/wgrad_study.md);
-                                wgrad_combine_kernel folds the slab. */
+    float* __restrict__ ws,  /* [K][RS*C] fp32, pre-zeroed, accumulated
+                                with atomicAdd across chunks */
     int N, int H, int W, int C, int K, int P, int Q,
     int R, int S, int sy, int sx, int py, int px, int nch, int mch) {
+    constexpr int MB = WG_BM;                // m per K-step
     constexpr int TCH = 32 * FT;             // tile channels per operand
     constexpr int TILE_ELEMS = MB * TCH;     // one operand tile
     constexpr int GI = MB * TCH / 2048;      // glds per wave per operand
@@ -1419,12 +860,14 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(
     // flight across the barrier while tile t computes (2*FT glds per wave
     // per tile-pair). FT=4 uses a 2-deep ring (96 KiB would exceed 1
     // block/CU headroom at 3).
-    constexpr int RING = (FT == 2 || MB == 32) ? 3 : 2;
+    constexpr int RING = (FT == 2) ? 3 : 2;
     const int nsteps = (int)((mend - mb0 + MB - 1) / MB);
     if (nsteps > 0) stage(0);
     if (RING > 2 && nsteps > 1) stage(1);
     for (int it = 0; it < nsteps; ++it) {
         if (RING > 2 && it + 1 < nsteps) {
+            static_assert(2 * GI == 4 || 2 * GI == 8,
+                          "counted ring: state the vmcnt for this GI");
             if constexpr (2 * GI == 4)
                 asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
             else
@@ -1444,91 +887,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(
         // DMA now flies over the MFMA cluster.
         const unsigned short* buf = lds + (it % RING) * 2 * TILE_ELEMS;
         short4_ a[FT][KSN][2], b[FT][KSN][2];   // [fi][ks][half]
-        if constexpr (ASMRD) {
-            // tr16 reads via inline asm, INVISIBLE to hipcc's wait
-            // inserter: the compiler otherwise (a) force-drains all
-            // outstanding LDS-DMA with vmcnt(0) before every visible
-            // tr-read cluster and (b) waits lgkmcnt(0) over ALL 8*FT
-            // reads before the first MFMA. Here the waits are counted by
-            // hand: ks=1's reads stay in flight under ks=0's MFMAs.
-            // stage() goes FIRST (max DMA flight time): its stray
-            // compiler lgkmcnt(0) then fires while nothing is
-            // outstanding, instead of draining the tr reads.
-            if (it + RING - 1 < nsteps) stage((it + RING - 1) % RING);
-            __builtin_amdgcn_sched_barrier(0);
-            #pragma unroll
-            for (int ks = 0; ks < KSN; ++ks)
-                #pragma unroll
-                for (int fi = 0; fi < FT; ++fi) {
-                    const int kb_a = wk * FT + fi;
-                    const int kb_b = wc * FT + fi;
-                    const int v0 = ks * 8 + lg * 2;
-                    const int p0 = (v0 >> 1);
-                    const int p1 = p0 + NWIN / 2;
-                    const unsigned short* pa =
-                        buf + kb_a * (MB * 16) + l15 * 4;
-                    const unsigned short* pb =
-                        buf + TILE_ELEMS + kb_b * (MB * 16) + l15 * 4;
-                    const unsigned aa0 = (unsigned)(unsigned long)
-                        (const __attribute__((address_space(3))) char*)
-                        (const char*)(pa + p0 * 64);
-                    const unsigned aa1 = (unsigned)(unsigned long)
-                        (const __attribute__((address_space(3))) char*)
-                        (const char*)(pa + p1 * 64);
-                    const unsigned ab0 = (unsigned)(unsigned long)
-                        (const __attribute__((address_space(3))) char*)
-                        (const char*)(pb + p0 * 64);
-                    const unsigned ab1 = (unsigned)(unsigned long)
-                        (const __attribute__((address_space(3))) char*)
-                        (const char*)(pb + p1 * 64);
-                    asm volatile("ds_read_b64_tr_b16 %0, %1"
-                                 : "=v"(a[fi][ks][0]) : "v"(aa0));
-                    asm volatile("ds_read_b64_tr_b16 %0, %1"
-                                 : "=v"(a[fi][ks][1]) : "v"(aa1));
-                    asm volatile("ds_read_b64_tr_b16 %0, %1"
-                                 : "=v"(b[fi][ks][0]) : "v"(ab0));
-                    asm volatile("ds_read_b64_tr_b16 %0, %1"
-                                 : "=v"(b[fi][ks][1]) : "v"(ab1));
-                }
-            __builtin_amdgcn_s_setprio(1);
-            #pragma unroll
-            for (int ks = 0; ks < KSN; ++ks) {
-                // sched_barrier(0) pins the MFMA clusters BETWEEN the
-                // counted waits: MFMAs are pure-register ops, so without
-                // it LLVM floats both clusters past both waits — and the
-                // asm-read results carry no wait-dependency at all (the
-                // hand-counted waits ARE the only correctness fence).
-                __builtin_amdgcn_sched_barrier(0);
-                if (ks == 0 && KSN == 2) {
-                    // lgkmcnt is 4-bit (max 15): for FT=4 the ideal
-                    // "leave 16 in flight" clamps to 15 (ds_reads return
-                    // in order, so this waits one extra ks=1 read)
-                    if constexpr (FT == 4)
-                        asm volatile("s_waitcnt lgkmcnt(15)" ::: "memory");
-                    else
-                        asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-                } else {
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                #pragma unroll
-                for (int ki = 0; ki < FT; ++ki)
-                    #pragma unroll
-                    for (int ci = 0; ci < FT; ++ci) {
-                        short8 af, bf;
-                        #pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            af[e] = a[ki][ks][0][e];
-                            af[e + 4] = a[ki][ks][1][e];
-                            bf[e] = b[ci][ks][0][e];
-                            bf[e + 4] = b[ci][ks][1][e];
-                        }
-                        acc[ki][ci] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                            af, bf, acc[ki][ci], 0, 0, 0);
-                    }
-            }
-            __builtin_amdgcn_s_setprio(0);
-        } else {
         #pragma unroll
         for (int fi = 0; fi < FT; ++fi)
             #pragma unroll
@@ -1571,7 +929,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(
                         af, bf, acc[ki][ci], 0, 0, 0);
                 }
         __builtin_amdgcn_s_setprio(0);
-        }
         // end barrier dropped: the next iteration's wait + top barrier
         // orders buffer reuse for every ring depth.
     }
@@ -1579,7 +936,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(
     // epilogue: out[i=k][j=c]; C/D map col=lane&15, row=(lane>>4)*4+jj
     const int fcol = lane & 15, frow0 = (lane >> 4) * 4;
     const long RSC = (long)R * S * C;
-    float* const wsb = TP ? ws + (long)chunk * K * RSC : ws;
     #pragma unroll
     for (int ki = 0; ki < FT; ++ki)
         #pragma unroll
@@ -1588,52 +944,9 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(
             for (int jj = 0; jj < 4; ++jj) {
                 const int kk = k0 + wk * 16 * FT + ki * 16 + frow0 + jj;
                 const int cc = c0 + wc * 16 * FT + ci * 16 + fcol;
-                if constexpr (TP)
-                    wsb[kk * RSC + (long)rs * C + cc] = acc[ki][ci][jj];
-                else
-                    atomicAdd(&wsb[kk * RSC + (long)rs * C + cc],
-                              acc[ki][ci][jj]);
+                atomicAdd(&ws[kk * RSC + (long)rs * C + cc],
+                          acc[ki][ci][jj]);
             }
-}
-
-// two-phase combine: ws[i] += sum_chunk part[chunk][i] (i over K*RSC,
-// float4-vectorized — C%64==0 so n%4==0). Streaming reads replace the
-// nch-deep DRAM atomic fan-in per address.
-__global__ __launch_bounds__(256) void wgrad_combine_kernel(
-    float* __restrict__ ws, const float* __restrict__ part, long n,
-    int nch) {
-    const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i >= n) return;
-    floatx4 s = *(const floatx4*)(part + i);
-    for (int j = 1; j < nch; ++j) {
-        const floatx4 p = *(const floatx4*)(part + (long)j * n + i);
-        s.x += p.x; s.y += p.y; s.z += p.z; s.w += p.w;
-    }
-    floatx4* w = (floatx4*)(ws + i);
-    const floatx4 w0 = *w;
-    s.x += w0.x; s.y += w0.y; s.z += w0.z; s.w += w0.w;
-    *w = s;
-}
-
-void wgrad_combine_launch(float* ws, const float* part, long n, int nch,
-                          hipStream_t stream) {
-    const long lanes = n / 4;
-    dim3 grid((unsigned)((lanes + 255) / 256));
-    hipLaunchKernelGGL(wgrad_combine_kernel, grid, dim3(256), 0, stream,
-                       ws, part, n, nch);
-}
-
-static bool wgrad_asm() {
-    // A/B knob FLUXDIST_WGRAD_ASM=1: hand-counted lgkm waits via
-    // inline-asm tr16 reads (ks-split MFMA overlap). Default OFF:
-    // measured -4.5% on the weighted wgrad total (2382 vs 2279 us) —
-    // the sched_barrier fences cost more scheduling freedom than the
-    // counted waits recover (profiles/ab_conv8.md campaign).
-    static bool v = [] {
-        const char* e = getenv("FLUXDIST_WGRAD_ASM");
-        return e && e[0] == '1';
-    }();
-    return v;
 }
 
 void conv_stem_wgrad_launch(const void* dy, const void* x, float* ws,
@@ -1648,17 +961,10 @@ void conv_stem_wgrad_launch(const void* dy, const void* x, float* ws,
     const int nch = (int)((M + STEM_MCH - 1) / STEM_MCH);
     dim3 grid((unsigned)(K / 64), 1u, (unsigned)(R * nch));
     const size_t shmem = 3 * 2 * (WG_BM * 64) * sizeof(unsigned short);
-    if (wgrad_asm())
-        hipLaunchKernelGGL((conv_wgrad_kernel<2, true, true>), grid,
-                           dim3(256), shmem, stream,
-                           (const unsigned short*)dy,
-                           (const unsigned short*)x, ws, N, Hp, Wp, 64, K,
-                           P, Q, R, 1, sy, sx, 0, 0, nch, STEM_MCH);
-    else
-        hipLaunchKernelGGL((conv_wgrad_kernel<2, true>), grid, dim3(256),
-                           shmem, stream, (const unsigned short*)dy,
-                           (const unsigned short*)x, ws, N, Hp, Wp, 64, K,
-                           P, Q, R, 1, sy, sx, 0, 0, nch, STEM_MCH);
+    hipLaunchKernelGGL((conv_wgrad_kernel<2, true>), grid, dim3(256), shmem,
+                       stream, (const unsigned short*)dy,
+                       (const unsigned short*)x, ws, N, Hp, Wp, 64, K, P, Q,
+                       R, 1, sy, sx, 0, 0, nch, STEM_MCH);
 }
 
 // pick the pixel-chunk size so the grid lands near `target` blocks:
@@ -1673,22 +979,14 @@ static int pick_mch(long M, long tiles, int target) {
     return (int)mch;
 }
 
-// tile/chunk plan — the single source of truth shared with the bindings
-// (which size the two-phase partial slab from nch; same pattern as
-// conv_igemm_plan after the fwd-stats workspace near-miss).
-void conv_wgrad_plan(long M, int C, int K, int R, int S,
-                     int* ft, int* mch, int* nch) {
-    // A/B: FLUXDIST_WGRAD_FT2=1 forces the 64x64 tile everywhere (its
-    // 48 KB 3-ring fits 3 blocks/CU vs FT4's 2 — the BK32 lesson)
-    static const bool force_ft2 = [] {
-        const char* e = getenv("FLUXDIST_WGRAD_FT2");
-        return e && e[0] == '1';
-    }();
+// tile/chunk plan: FT (fragments per wave axis), pixels per chunk, chunks
+static void conv_wgrad_plan(long M, int C, int K, int R, int S,
+                            int* ft, int* mch, int* nch) {
     // FT=4 quarters the block count; only worth it when the grid still
     // fills the 256 CUs (small-M 1x1 shapes measured 1.4x slower on it)
     const long tiles4 = (long)(K / 128) * (C / 128) * R * S;
     const long blocks4_max = tiles4 * ((M + WG_MCH - 1) / WG_MCH);
-    if (!force_ft2 && K % 128 == 0 && C % 128 == 0 && blocks4_max >= 192) {
+    if (K % 128 == 0 && C % 128 == 0 && blocks4_max >= 192) {
         *ft = 4;
         *mch = pick_mch(M, tiles4, 768);
     } else {
@@ -1698,86 +996,29 @@ void conv_wgrad_plan(long M, int C, int K, int R, int S,
     *nch = (int)((M + *mch - 1) / *mch);
 }
 
-bool conv_wgrad_two_phase() {
-    // FLUXDIST_WGRAD_2PH=1: chunk blocks plain-store private partials,
-    // one combine kernel folds them (no DRAM atomics, no fill needed on
-    // the slab — docs/wgrad_study.md option 1). Mutually exclusive with
-    // the MB32 A/B knob, whose launch path ignores the slab — combining
-    // an unwritten slab would corrupt ws.
-    static const bool v = [] {
-        const char* e = getenv("FLUXDIST_WGRAD_2PH");
-        const char* m = getenv("FLUXDIST_WGRAD_MB32");
-        return e && e[0] == '1' && !(m && m[0] == '1');
-    }();
-    return v;
-}
-
 void conv_wgrad_launch(const void* dy, const void* x, float* ws,
                        int N, int H, int W, int C, int K, int P, int Q,
                        int R, int S, int sy, int sx, int py, int px,
-                       hipStream_t stream, float* part) {
+                       hipStream_t stream) {
     const long M = (long)N * P * Q;
     int FTp, mch, nch;
     conv_wgrad_plan(M, C, K, R, S, &FTp, &mch, &nch);
     if (FTp == 4) {
         dim3 grid((unsigned)(K / 128), (unsigned)(C / 128),
                   (unsigned)(R * S * nch));
-        static const bool mb32 = [] {
-            // A/B knob: FT4 with a 32-pixel K-step — 48 KB 3-ring at 3
-            // blocks/CU, same 4:1 MFMA:glds ratio (the BK32 recipe)
-            const char* e = getenv("FLUXDIST_WGRAD_MB32");
-            return e && e[0] == '1';
-        }();
-        if (mb32) {
-            const size_t shmem = 3 * 2 * (32 * 128) * sizeof(unsigned short);
-            hipLaunchKernelGGL((conv_wgrad_kernel<4, false, false, 32>),
-                               grid, dim3(256), shmem, stream,
-                               (const unsigned short*)dy,
-                               (const unsigned short*)x, ws, N, H, W, C, K,
-                               P, Q, R, S, sy, sx, py, px, nch, mch);
-            return;
-        }
         const size_t shmem = 2 * 2 * (WG_BM * 128) * sizeof(unsigned short);
-        if (part)
-            hipLaunchKernelGGL((conv_wgrad_kernel<4, false, false, WG_BM,
-                                                  true>),
-                               grid, dim3(256), shmem, stream,
-                               (const unsigned short*)dy,
-                               (const unsigned short*)x, part, N, H, W, C,
-                               K, P, Q, R, S, sy, sx, py, px, nch, mch);
-        else if (wgrad_asm())
-            hipLaunchKernelGGL((conv_wgrad_kernel<4, false, true>), grid,
-                               dim3(256), shmem, stream,
-                               (const unsigned short*)dy,
-                               (const unsigned short*)x, ws, N, H, W, C, K,
-                               P, Q, R, S, sy, sx, py, px, nch, mch);
-        else
-            hipLaunchKernelGGL(conv_wgrad_kernel<4>, grid, dim3(256), shmem,
-                               stream, (const unsigned short*)dy,
-                               (const unsigned short*)x, ws, N, H, W, C, K,
-                               P, Q, R, S, sy, sx, py, px, nch, mch);
+        hipLaunchKernelGGL(conv_wgrad_kernel<4>, grid, dim3(256), shmem,
+                           stream, (const unsigned short*)dy,
+                           (const unsigned short*)x, ws, N, H, W, C, K,
+                           P, Q, R, S, sy, sx, py, px, nch, mch);
     } else {
         dim3 grid((unsigned)(K / 64), (unsigned)(C / 64),
                   (unsigned)(R * S * nch));
         const size_t shmem = 3 * 2 * (WG_BM * 64) * sizeof(unsigned short);
-        if (part)
-            hipLaunchKernelGGL((conv_wgrad_kernel<2, false, false, WG_BM,
-                                                  true>),
-                               grid, dim3(256), shmem, stream,
-                               (const unsigned short*)dy,
-                               (const unsigned short*)x, part, N, H, W, C,
-                               K, P, Q, R, S, sy, sx, py, px, nch, mch);
-        else if (wgrad_asm())
-            hipLaunchKernelGGL((conv_wgrad_kernel<2, false, true>), grid,
-                               dim3(256), shmem, stream,
-                               (const unsigned short*)dy,
-                               (const unsigned short*)x, ws, N, H, W, C, K,
-                               P, Q, R, S, sy, sx, py, px, nch, mch);
-        else
-            hipLaunchKernelGGL(conv_wgrad_kernel<2>, grid, dim3(256), shmem,
-                               stream, (const unsigned short*)dy,
-                               (const unsigned short*)x, ws, N, H, W, C, K,
-                               P, Q, R, S, sy, sx, py, px, nch, mch);
+        hipLaunchKernelGGL(conv_wgrad_kernel<2>, grid, dim3(256), shmem,
+                           stream, (const unsigned short*)dy,
+                           (const unsigned short*)x, ws, N, H, W, C, K,
+                           P, Q, R, S, sy, sx, py, px, nch, mch);
     }
 }
 
