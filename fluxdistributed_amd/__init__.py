@@ -34,7 +34,8 @@ from .parallel.gradtree import (  # noqa: F401
     check_nans,
 )
 from .parallel.task_ddp import prepare_training, train, train_step  # noqa: F401
-from .data.imagenet import minibatch, train_solutions, labels  # noqa: F401
+from .data.imagenet import minibatch, minibatch_raw, train_solutions, labels  # noqa: F401
+from .data.preprocess import RawBatch, pack_images, preprocess_batch  # noqa: F401
 from .utils.metrics import topkaccuracy  # noqa: F401
 
 from . import models, ops, parallel, data, utils  # noqa: F401

@@ -683,7 +683,61 @@ at::Tensor gap_bwd(at::Tensor gy, int64_t H, int64_t W) {
     return gx;
 }
 
+// ---- device-side image preprocessing (preprocess.hip) ---------------------
+// arena: 1-D uint8, meta: [N][PREPROCESS_META_INTS] int32 (layout in
+// fda_kernels.h), both on the same device. Returns [N,3,crop,crop]
+// channels_last, fp32 or bf16.
+at::Tensor preprocess_batch(at::Tensor arena, at::Tensor meta, int64_t crop,
+                            bool normalize, bool standardize, bool bf16) {
+    TORCH_CHECK(arena.is_cuda() && meta.is_cuda(),
+                "preprocess_batch: device tensors required (a CPU tensor here "
+                "would fault the GPU with a host pointer)");
+    TORCH_CHECK(arena.device() == meta.device(),
+                "preprocess_batch: arena and meta must share a device");
+    TORCH_CHECK(arena.scalar_type() == at::kByte && arena.dim() == 1 &&
+                arena.is_contiguous(),
+                "preprocess_batch: arena must be 1-D contiguous uint8");
+    TORCH_CHECK(meta.scalar_type() == at::kInt && meta.dim() == 2 &&
+                meta.size(1) == fda::PREPROCESS_META_INTS &&
+                meta.is_contiguous(),
+                "preprocess_batch: meta must be contiguous int32 [N][",
+                fda::PREPROCESS_META_INTS, "]");
+    TORCH_CHECK((reinterpret_cast<uintptr_t>(arena.data_ptr()) & 15) == 0,
+                "preprocess_batch: arena must be 16-byte aligned");
+    TORCH_CHECK(crop >= 1 && crop <= 4096,
+                "preprocess_batch: crop must be in [1, 4096], got ", crop);
+    const int64_t N = meta.size(0);
+    const int tiles = fda::preprocess_tiles((int)crop);
+    TORCH_CHECK(N * tiles < (int64_t)1 << 31,
+                "preprocess_batch: batch too large");
+    auto out = at::empty({N, 3, crop, crop},
+                         arena.options()
+                             .dtype(bf16 ? at::kBFloat16 : at::kFloat)
+                             .memory_format(at::MemoryFormat::ChannelsLast));
+    if (N == 0) return out;
+    auto scratch = at::empty({N, crop, crop, 3},
+                             arena.options().dtype(at::kFloat));
+    auto partials = at::empty({N, tiles, 2},
+                              arena.options().dtype(at::kDouble));
+    auto stream = cur_stream();
+    fda::preprocess_resample_launch(arena.data_ptr<uint8_t>(), arena.numel(),
+                                    meta.data_ptr<int32_t>(),
+                                    scratch.data_ptr<float>(),
+                                    partials.data_ptr<double>(), (int)N,
+                                    (int)crop, normalize, stream);
+    fda::preprocess_apply_launch(scratch.data_ptr<float>(),
+                                 partials.data_ptr<double>(), out.data_ptr(),
+                                 (int)N, (int)crop, standardize,
+                                 bf16 ? DT::BF16 : DT::F32, stream);
+    return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+    m.def("preprocess_batch", &preprocess_batch, pybind11::arg("arena"),
+          pybind11::arg("meta"), pybind11::arg("crop"),
+          pybind11::arg("normalize"), pybind11::arg("standardize"),
+          pybind11::arg("bf16"),
+          "uint8 image arena -> resized, cropped, normalized NHWC batch");
     m.def("ce_fwd", &ce_fwd, "fused logit cross-entropy fwd (loss + dlogits)");
     m.def("add_relu_fwd", &add_relu_fwd);
     m.def("add_relu_bwd", &add_relu_bwd);

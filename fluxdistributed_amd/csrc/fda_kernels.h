@@ -170,6 +170,32 @@ void bias_add_rows_bf16_launch(void* y, const void* bias, long M, int ldl,
 void colsum_accum_bf16_launch(void* g, const void* dy, long M, int ldl,
                               int Cvalid, hipStream_t s);
 
+// Device-side image preprocessing (preprocess.hip): ragged uint8 HWC RGB
+// images -> low-pass + bilinear resize + centre crop + normalize
+// (+ per-image standardize) -> [N][crop][crop][3] fp32 / bf16.
+//   arena: all images packed back to back, each at a 16-byte-aligned offset.
+//   meta:  one row of PREPROCESS_META_INTS int32 words per image:
+//     [0],[1] int64 byte offset into the arena (low word, high word)
+//     [2] h   [3] w      source size
+//     [4] nh  [5] nw     size after the resize (min(nh, nw) == resize)
+//     [6] top [7] left   crop origin in the resized image
+//     [8] r              Gaussian radius (0 = no blur)
+//     [9] sigma          float bits (unused when r == 0)
+//   A row that would read outside the arena, or with r >= min(h, w), yields
+//   NaNs for that image instead of being trusted.
+// resample writes the fp32 scratch [N][crop][crop][3] and per-tile
+// sum / sum-of-squares partials [N][preprocess_tiles(crop)][2] (double);
+// apply folds them per image (standardize) and writes the final dtype.
+constexpr int PREPROCESS_META_INTS = 10;
+int preprocess_tiles(int crop);
+void preprocess_resample_launch(const uint8_t* arena, int64_t arena_bytes,
+                                const int32_t* meta, float* scratch,
+                                double* partials, int N, int crop,
+                                bool normalize, hipStream_t s);
+void preprocess_apply_launch(const float* scratch, const double* partials,
+                             void* out, int N, int crop, bool standardize,
+                             DT dt, hipStream_t s);
+
 // flat fused optimizers. P: param dtype; M/V/S fp32; G param dtype.
 void sgd_step_launch(void* P, const void* G, float* M, float* V, int64_t n,
                      float lr, float mom, float wd, bool nesterov,

@@ -19,7 +19,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .preprocess import preprocess
+from .preprocess import RawBatch, pack_images, preprocess
 
 
 def labels(root: str) -> List[Tuple[str, str]]:
@@ -120,3 +120,33 @@ def minibatch(root: str, key: List[Tuple[str, int]], nsamples: int = 32,
         for f in futs:
             f.result()  # re-raise decode errors; barrier
     return x, y
+
+
+def _decode(path: str) -> np.ndarray:
+    """Decode one JPEG to HWC uint8 RGB — all `_fproc` does before its float
+    work."""
+    from PIL import Image
+
+    with Image.open(path) as im:
+        return np.asarray(im.convert("RGB"), dtype=np.uint8)
+
+
+def minibatch_raw(root: str, key: List[Tuple[str, int]], nsamples: int = 32,
+                  ids: Optional[Sequence[int]] = None, num_workers: int = 8,
+                  rng: Optional[random.Random] = None, resize: int = 256,
+                  crop: int = 224) -> Tuple[RawBatch, torch.Tensor]:
+    """`minibatch` with the preprocessing left to the consumer: the workers
+    only decode, and the images come back packed as a RawBatch for
+    `preprocess_batch(raw, standardize=True)` (on the device, or on the CPU
+    where it reproduces `minibatch`'s x). Same sampling, thread pool and
+    hard join as `minibatch`. Returns (RawBatch, y[N] i64)."""
+    rng = rng or random
+    if ids is None:
+        ids = [rng.randrange(len(key)) for _ in range(nsamples)]
+    rows = [key[i] for i in ids]
+    y = torch.tensor([cls for _, cls in rows], dtype=torch.long)
+    with ThreadPoolExecutor(max_workers=num_workers) as pool:
+        futs = [pool.submit(_decode, makepaths(img_id, root))
+                for img_id, _ in rows]
+        images = [f.result() for f in futs]  # re-raise decode errors; barrier
+    return pack_images(images, resize=resize, crop=crop), y

@@ -22,13 +22,19 @@ class PrefetchLoader:
     """Iterable: next() yields device-resident (x, y) batches.
 
     make_batch: () -> (x, y) host tensors (the loader function).
+    device_transform: optional (raw, device) -> x. When given, make_batch
+    returns (RawBatch, y) (data.imagenet.minibatch_raw): the producer thread
+    only pins the raw arena and meta, and next() uploads them and runs the
+    transform (data.preprocess.preprocess_batch) on the side stream.
     """
 
     _SENTINEL = object()
 
     def __init__(self, make_batch: Callable[[], tuple], device=None,
-                 buffersize: int = 5, pin: Optional[bool] = None):
+                 buffersize: int = 5, pin: Optional[bool] = None,
+                 device_transform: Optional[Callable] = None):
         self.make_batch = make_batch
+        self.device_transform = device_transform
         self.device = device
         self.gpu = is_real_gpu(device)
         self.pin = self.gpu if pin is None else pin
@@ -52,6 +58,29 @@ class PrefetchLoader:
             self._exc = e
             self.q.put(self._SENTINEL)
 
+    def _next_transformed(self, raw, y):
+        # Upload and transform happen here, on the consumer thread: the
+        # producer does host work only (a RawBatch pins like a tensor), since
+        # a kernel launched from it could land in the middle of the graph
+        # engine's stream capture.
+        if not self.gpu:
+            return self.device_transform(raw, self.device), y
+        with torch.cuda.stream(self.copy_stream):
+            rd = raw.to(self.device, non_blocking=True)
+            xd = self.device_transform(rd, self.device)
+            yd = y.to(self.device, non_blocking=True)
+        evt = torch.cuda.Event()
+        evt.record(self.copy_stream)
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(evt)
+        # same allocator contract as below; the uploaded raw arena is only
+        # ever read on copy_stream and goes back to that stream's pool
+        xd.record_stream(cur)
+        yd.record_stream(cur)
+        # pinned host tensors must outlive the async copy
+        self._prev_batch = (raw, y)
+        return xd, yd
+
     def __iter__(self):
         return self
 
@@ -60,6 +89,8 @@ class PrefetchLoader:
         if item is self._SENTINEL:
             raise RuntimeError("loader thread failed") from self._exc
         x, y = item
+        if self.device_transform is not None:
+            return self._next_transformed(x, y)
         if not self.gpu:
             return x, y
         with torch.cuda.stream(self.copy_stream):

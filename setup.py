@@ -23,6 +23,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "bn_act.hip"),
         os.path.join(CSRC, "pool.hip"),
         os.path.join(CSRC, "conv_igemm.hip"),
+        os.path.join(CSRC, "preprocess.hip"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],

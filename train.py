@@ -56,6 +56,11 @@ def parse_args():
                    help="imagenet: images per minibatch (default: --batch)")
     p.add_argument("--classes", type=int, nargs="*", default=None,
                    help="imagenet: restrict to these class indices")
+    p.add_argument("--device-preprocess", action="store_true",
+                   help="imagenet: loader workers only decode; resize, crop, "
+                        "normalize and standardize run on the device (HIP "
+                        "kernel on the loader's side stream; on a CPU device "
+                        "the host preprocess runs instead)")
     p.add_argument("--buffersize", type=int, default=5)
     p.add_argument("--val-every", type=int, default=50)
     p.add_argument("--log-every", type=int, default=10)
@@ -99,7 +104,32 @@ def make_batch_fn(args, rank=0, world=1):
     shard = shard_key(key, rank, world, seed=args.seed)
     rng = random.Random(args.seed * 7_919 + rank)
     ns = args.nsamples or args.batch
+    if device_preprocess(args):
+        from fluxdistributed_amd.data.imagenet import minibatch_raw
+
+        return lambda n=None: minibatch_raw(root, shard, nsamples=n or ns,
+                                            rng=rng)
     return lambda n=None: minibatch(root, shard, nsamples=n or ns, rng=rng)
+
+
+def device_preprocess(args) -> bool:
+    """--device-preprocess only has an effect on a real dataset."""
+    return bool(getattr(args, "device_preprocess", False)) and \
+        args.data != "synthetic"
+
+
+def make_device_transform(args):
+    """The loader's device_transform for --device-preprocess (None without
+    it): (RawBatch, device) -> x in the training dtype, standardized per
+    image as `minibatch` does."""
+    if not device_preprocess(args):
+        return None
+    from fluxdistributed_amd.data.preprocess import preprocess_batch
+
+    dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
+    return lambda raw, dev: preprocess_batch(
+        raw, device=dev if isinstance(dev, torch.device) else None,
+        standardize=True, dtype=dtype)
 
 
 def run_task(args):
@@ -111,12 +141,19 @@ def run_task(args):
         model = model.to(memory_format=torch.channels_last)
         if args.dtype == "bf16":
             model = to_mixed_bf16(model)
+    transform = make_device_transform(args)
+    loader_factory = None
+    if transform is not None:
+        loader_factory = lambda f, d: PrefetchLoader(  # noqa: E731
+            f, device=d, buffersize=args.buffersize,
+            device_transform=transform)
     st = prepare_training(
         model,
         [make_batch_fn(args, rank=i, world=len(devices))
          for i in range(len(devices))],
         devices, make_opt_factory(args),
         nsamples=args.batch, buffersize=args.buffersize,
+        loader_factory=loader_factory,
     )
     if args.resume:
         for r in st.replicas:
@@ -157,7 +194,8 @@ def run_process(args):
         load_checkpoint(args.resume, model, opt)
 
     batch_fn = make_batch_fn(args, rank, world)
-    loader = PrefetchLoader(batch_fn, device=device, buffersize=args.buffersize)
+    loader = PrefetchLoader(batch_fn, device=device, buffersize=args.buffersize,
+                            device_transform=make_device_transform(args))
     model_, opt_, stats = syncgrads_worker(
         model, opt, logit_cross_entropy, loader, steps=args.steps,
         checkpoint_every=args.checkpoint_every,
