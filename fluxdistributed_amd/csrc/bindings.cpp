@@ -27,13 +27,80 @@ std::pair<int64_t, int64_t> nhwc_rows(const at::Tensor& x) {
     return {x.size(0) * x.size(2) * x.size(3), x.size(1)};
 }
 
+// ---- operand checks for the non-conv entry points -------------------------
+// Every pointer a kernel receives is checked here first: a host tensor or a
+// short buffer would otherwise become a wild access on the GPU. Each entry
+// point makes its shape, dtype and layout checks first and calls
+// check_device last, right before it allocates and launches, so that every
+// refusal can be exercised on a machine without a GPU.
+
+// All (defined) tensors live on one GPU.
+void check_device(const char* op, std::initializer_list<at::Tensor> ts) {
+    const at::Tensor* first = nullptr;
+    for (const auto& t : ts) {
+        if (!t.defined()) continue;
+        TORCH_CHECK(t.is_cuda(), op,
+                    ": device tensors required (a CPU tensor here would "
+                    "fault the GPU with a host pointer)");
+        if (first == nullptr) first = &t;
+        TORCH_CHECK(t.device() == first->device(), op,
+                    ": all tensors must share a device");
+    }
+}
+
+// A contiguous tensor of `dtype` with exactly n elements.
+void check_flat(const char* op, const char* name, const at::Tensor& t,
+                at::ScalarType dtype, int64_t n) {
+    TORCH_CHECK(t.scalar_type() == dtype && t.is_contiguous() &&
+                    t.numel() == n,
+                op, ": ", name, " must be contiguous ", dtype, " with ", n,
+                " elements");
+}
+
+// `t` is channels_last like the activation `ref`, with its dtype and sizes.
+// (Not a stride comparison: strides of size-1 dimensions are arbitrary.)
+void check_like(const char* op, const char* name, const at::Tensor& t,
+                const at::Tensor& ref, const char* ref_name) {
+    TORCH_CHECK(t.scalar_type() == ref.scalar_type() &&
+                    t.sizes() == ref.sizes() &&
+                    t.is_contiguous(at::MemoryFormat::ChannelsLast),
+                op, ": ", name, " must match ", ref_name,
+                " in dtype, shape and channels_last layout");
+}
+
+// Channel count of a 16 B/lane kernel: a multiple of V = 8 (bf16) / 4 (fp32).
+int check_vec_channels(const char* op, const at::Tensor& x, int64_t C) {
+    const int V = dt_of(x) == DT::BF16 ? 8 : 4;
+    TORCH_CHECK(C % V == 0, op, ": C must be divisible by ", V, ", got ", C);
+    return V;
+}
+
+// Pooled output size; refuses geometry the argmax byte or the size formula
+// cannot represent.
+std::pair<int, int> pool_out_hw(const char* op, int64_t H, int64_t W,
+                                int64_t KH, int64_t KW, int64_t S, int64_t P) {
+    TORCH_CHECK(KH >= 1 && KW >= 1 && KH * KW <= 255, op,
+                ": pool window must have 1..255 taps (the argmax is one "
+                "byte), got ", KH, "x", KW);
+    TORCH_CHECK(S >= 1 && P >= 0, op, ": pool needs stride >= 1 and "
+                "padding >= 0, got S=", S, " P=", P);
+    TORCH_CHECK(H + 2 * P >= KH && W + 2 * P >= KW, op,
+                ": pool window > input");
+    return {(int)((H + 2 * P - KH) / S + 1), (int)((W + 2 * P - KW) / S + 1)};
+}
+
 std::tuple<at::Tensor, at::Tensor> ce_fwd(at::Tensor logits, at::Tensor target) {
     // accepts row-strided logits (stride(1)==1): the FC head's %64-padded
     // buffer is read in place, no contiguity copy
     TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 &&
                 logits.stride(0) >= logits.size(1));
-    TORCH_CHECK(target.scalar_type() == at::kLong && target.is_contiguous());
     const int N = (int)logits.size(0), C = (int)logits.size(1);
+    dt_of(logits);
+    TORCH_CHECK(target.scalar_type() == at::kLong && target.is_contiguous() &&
+                    target.numel() == N,
+                "ce_fwd: target must be contiguous int64 with one class "
+                "index per row");
+    check_device("ce_fwd", {logits, target});
     auto loss = at::zeros({}, logits.options().dtype(at::kFloat));
     auto dlogits = at::empty({N, C}, logits.options());
     fda::ce_fwd_launch(logits.data_ptr(), target.data_ptr<int64_t>(),
@@ -44,16 +111,22 @@ std::tuple<at::Tensor, at::Tensor> ce_fwd(at::Tensor logits, at::Tensor target) 
     return {loss, dlogits};
 }
 
+// Both operands of an elementwise op in one dense layout (channels_last for
+// 4-D), after checking that they agree and live on the GPU.
+std::pair<at::Tensor, at::Tensor> elementwise_pair(const char* op,
+                                                   const at::Tensor& a,
+                                                   const at::Tensor& b) {
+    TORCH_CHECK(a.sizes() == b.sizes() && a.scalar_type() == b.scalar_type(),
+                op, ": operands must agree in shape and dtype");
+    dt_of(a);
+    check_device(op, {a, b});
+    const auto fmt = a.dim() == 4 ? at::MemoryFormat::ChannelsLast
+                                  : at::MemoryFormat::Contiguous;
+    return {a.contiguous(fmt), b.contiguous(fmt)};
+}
+
 at::Tensor add_relu_fwd(at::Tensor x, at::Tensor r) {
-    TORCH_CHECK(x.sizes() == r.sizes() && x.scalar_type() == r.scalar_type());
-    at::Tensor xc = x, rc = r;
-    if (x.dim() == 4) {
-        xc = x.contiguous(at::MemoryFormat::ChannelsLast);
-        rc = r.contiguous(at::MemoryFormat::ChannelsLast);
-    } else {
-        xc = x.contiguous();
-        rc = r.contiguous();
-    }
+    auto [xc, rc] = elementwise_pair("add_relu_fwd", x, r);
     auto out = at::empty_like(xc);
     fda::add_relu_fwd_launch(xc.data_ptr(), rc.data_ptr(), out.data_ptr(),
                              xc.numel(), dt_of(xc), cur_stream());
@@ -61,47 +134,60 @@ at::Tensor add_relu_fwd(at::Tensor x, at::Tensor r) {
 }
 
 at::Tensor add_relu_bwd(at::Tensor gout, at::Tensor out) {
-    TORCH_CHECK(gout.sizes() == out.sizes());
-    auto gc = gout, oc = out;
-    if (gout.dim() == 4) {
-        gc = gout.contiguous(at::MemoryFormat::ChannelsLast);
-        oc = out.contiguous(at::MemoryFormat::ChannelsLast);
-    } else {
-        gc = gout.contiguous();
-        oc = out.contiguous();
-    }
+    auto [gc, oc] = elementwise_pair("add_relu_bwd", gout, out);
     auto gx = at::empty_like(gc);
     fda::add_relu_bwd_launch(gc.data_ptr(), oc.data_ptr(), gx.data_ptr(),
                              gc.numel(), dt_of(gc), cur_stream());
     return gx;
 }
 
-// Forward statistics -> scale/shift in ws[2C..4C), save_mean, save_invstd
-// (and the running-stat update): from the producing conv's epilogue
-// partials, BN's own stats pass, or (eval) the running stats. Shared by
-// bn_act_fwd and the fused BN+ReLU+pool forward.
+// Shape/dtype/layout checks shared by the two BN forward entry points;
+// returns (rows, C). Device check is left to the caller (it comes last).
+std::pair<int64_t, int64_t> check_bn_fwd_operands(
+    const char* op, const at::Tensor& x, const at::Tensor& weight,
+    const at::Tensor& bias, const at::Tensor& running_mean,
+    const at::Tensor& running_var, bool training,
+    const c10::optional<at::Tensor>& conv_part) {
+    auto [rows, C] = nhwc_rows(x);
+    const int V = check_vec_channels(op, x, C);
+    TORCH_CHECK((C / V) >= 256 ? (C / V) % 256 == 0 : 256 % (C / V) == 0,
+                "unsupported channel count ", C);
+    TORCH_CHECK(weight.scalar_type() == at::kFloat, "BN params must be fp32");
+    check_flat(op, "weight", weight, at::kFloat, C);
+    check_flat(op, "bias", bias, at::kFloat, C);
+    check_flat(op, "running_mean", running_mean, at::kFloat, C);
+    check_flat(op, "running_var", running_var, at::kFloat, C);
+    if (training)
+        TORCH_CHECK(C % 64 == 0, "training BN needs C % 64 == 0, got ", C);
+    if (training && conv_part.has_value())
+        TORCH_CHECK(conv_part->dim() == 3 && conv_part->size(0) >= 1 &&
+                        conv_part->size(1) == 2 && conv_part->size(2) == C &&
+                        conv_part->scalar_type() == at::kFloat &&
+                        conv_part->is_contiguous(),
+                    op, ": conv_part must be contiguous fp32 [NB][2][C]");
+    return {rows, C};
+}
+
+// Forward statistics -> scale/shift in ws (2*C floats), save_mean,
+// save_invstd (and the running-stat update): from the producing conv's
+// epilogue partials, BN's own stats pass, or (eval) the running stats.
+// Shared by bn_act_fwd and the fused BN+ReLU+pool forward; operands already
+// checked.
 std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_fwd_finalize(
     const at::Tensor& x, const at::Tensor& weight, const at::Tensor& bias,
     at::Tensor& running_mean, at::Tensor& running_var, bool training,
     double momentum, double eps, const c10::optional<at::Tensor>& conv_part) {
     auto [rows, C] = nhwc_rows(x);
-    const int V = dt_of(x) == DT::BF16 ? 8 : 4;
-    TORCH_CHECK(C % V == 0, "C must be divisible by ", V);
-    TORCH_CHECK((C / V) >= 256 ? (C / V) % 256 == 0 : 256 % (C / V) == 0,
-                "unsupported channel count ", C);
-    TORCH_CHECK(weight.scalar_type() == at::kFloat, "BN params must be fp32");
     auto fopts = x.options().dtype(at::kFloat);
-    auto ws = at::empty({4 * C}, fopts);
+    auto ws = at::empty({2 * C}, fopts);
     auto save_mean = at::empty({C}, fopts);
     auto save_invstd = at::empty({C}, fopts);
     auto stream = cur_stream();
 
     if (training && conv_part.has_value()) {
         // stats already accumulated by the producing conv's epilogue
-        auto& cp = *conv_part;
-        TORCH_CHECK(cp.dim() == 3 && cp.size(1) == 2 && cp.size(2) == C);
-        const float* pp = cp.data_ptr<float>();
-        int NB = (int)cp.size(0);
+        const float* pp = conv_part->data_ptr<float>();
+        int NB = (int)conv_part->size(0);
         at::Tensor p2;
         if (NB > 1024) {
             // layer-1-sized partial sets (~4700 m-tiles) fold at full
@@ -114,14 +200,13 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_fwd_finalize(
             pp = p2.data_ptr<float>();
             NB = NB2;
         }
-        fda::bn_finalize_from_partials_launch(
-            pp, NB, weight.data_ptr<float>(),
+        fda::bn_fwd_finalize_launch(
+            pp, NB, (int)C, 0, weight.data_ptr<float>(),
             bias.data_ptr<float>(), running_mean.data_ptr<float>(),
             running_var.data_ptr<float>(), save_mean.data_ptr<float>(),
             save_invstd.data_ptr<float>(), ws.data_ptr<float>(), rows,
             (int)C, (float)momentum, (float)eps, stream);
     } else if (training) {
-        TORCH_CHECK(C % 64 == 0, "training BN needs C % 64 == 0, got ", C);
         auto part = at::empty({fda::bn_stats_partial_floats((int)C, rows, dt_of(x))},
                               fopts);
         fda::bn_stats_launch(x.data_ptr(), ws.data_ptr<float>(),
@@ -133,13 +218,11 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_fwd_finalize(
                              save_invstd.data_ptr<float>(), rows, (int)C,
                              (float)momentum, (float)eps, dt_of(x), stream);
     } else {
-        fda::bn_finalize_launch(ws.data_ptr<float>(), weight.data_ptr<float>(),
-                                bias.data_ptr<float>(),
-                                running_mean.data_ptr<float>(),
-                                running_var.data_ptr<float>(),
-                                save_mean.data_ptr<float>(),
-                                save_invstd.data_ptr<float>(), rows, (int)C,
-                                training, (float)momentum, (float)eps, stream);
+        fda::bn_eval_finalize_launch(
+            ws.data_ptr<float>(), weight.data_ptr<float>(),
+            bias.data_ptr<float>(), running_mean.data_ptr<float>(),
+            running_var.data_ptr<float>(), save_mean.data_ptr<float>(),
+            save_invstd.data_ptr<float>(), (int)C, (float)eps, stream);
     }
     return {ws, save_mean, save_invstd};
 }
@@ -148,19 +231,45 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_act_fwd(
     at::Tensor x, at::Tensor weight, at::Tensor bias, at::Tensor running_mean,
     at::Tensor running_var, bool training, double momentum, double eps,
     bool relu, at::Tensor residual, c10::optional<at::Tensor> conv_part) {
-    auto [rows, C] = nhwc_rows(x);
+    auto [rows, C] = check_bn_fwd_operands("bn_act_fwd", x, weight, bias,
+                                           running_mean, running_var,
+                                           training, conv_part);
     const bool has_res = residual.defined() && residual.numel() > 0;
     at::Tensor resc;
-    if (has_res) resc = residual.contiguous(at::MemoryFormat::ChannelsLast);
+    if (has_res) {
+        resc = residual.contiguous(at::MemoryFormat::ChannelsLast);
+        check_like("bn_act_fwd", "residual", resc, x, "x");
+    }
+    check_device("bn_act_fwd",
+                 {x, weight, bias, running_mean, running_var, resc,
+                  conv_part.value_or(at::Tensor())});
     auto [ws, save_mean, save_invstd] =
         bn_fwd_finalize(x, weight, bias, running_mean, running_var, training,
                         momentum, eps, conv_part);
     auto out = at::empty_like(x);
-    auto stream = cur_stream();
     fda::bn_apply_launch(x.data_ptr(), has_res ? resc.data_ptr() : nullptr,
                          out.data_ptr(), ws.data_ptr<float>(), rows, (int)C,
-                         relu, dt_of(x), stream);
+                         relu, dt_of(x), cur_stream());
     return {out, save_mean, save_invstd};
+}
+
+// gw/gb of the two BN backward entry points: the caller's fp32 flat-G slices
+// (direct grad: the finalize += 's into them, `direct` is true) or fresh
+// [C] buffers. Both slices or neither; each must hold exactly C floats,
+// because the finalize writes C floats through it.
+std::tuple<at::Tensor, at::Tensor, bool> bn_bwd_grad_targets(
+    const char* op, const at::Tensor& x, int64_t C,
+    const c10::optional<at::Tensor>& gw_out,
+    const c10::optional<at::Tensor>& gb_out) {
+    TORCH_CHECK(gw_out.has_value() == gb_out.has_value(), op,
+                ": gw_out and gb_out must be given together");
+    if (gw_out.has_value()) {
+        check_flat(op, "gw_out", *gw_out, at::kFloat, C);
+        check_flat(op, "gb_out", *gb_out, at::kFloat, C);
+        return {*gw_out, *gb_out, true};
+    }
+    auto fopts = x.options().dtype(at::kFloat);
+    return {at::empty({C}, fopts), at::empty({C}, fopts), false};
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_act_bwd(
@@ -171,22 +280,26 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_act_bwd(
     // gw_out/gb_out set: fp32 flat-G slices, written += (direct grad).
     // bias set on a non-residual ReLU BN: both kernels recompute the ReLU
     // mask from x (the forward's own expression) and never read `out`.
+    const char* op = "bn_act_bwd";
     auto [rows, C] = nhwc_rows(x);
+    dt_of(x);
+    TORCH_CHECK(C % 64 == 0, "BN bwd needs C % 64 == 0, got ", C);
     auto gc = gout.contiguous(at::MemoryFormat::ChannelsLast);
+    check_like(op, "gout", gc, x, "x");
+    check_like(op, "out", out, x, "x");
+    check_flat(op, "weight", weight, at::kFloat, C);
+    check_flat(op, "save_mean", save_mean, at::kFloat, C);
+    check_flat(op, "save_invstd", save_invstd, at::kFloat, C);
+    const bool xmask = relu && !want_gres && bias.has_value();
+    if (xmask) check_flat(op, "bias", *bias, at::kFloat, C);
+    auto [gw, gb, direct] = bn_bwd_grad_targets(op, x, C, gw_out, gb_out);
+    check_device(op, {x, gc, out, weight, save_mean, save_invstd, gw, gb,
+                      xmask ? *bias : at::Tensor()});
+
     auto fopts = x.options().dtype(at::kFloat);
-    auto ws = at::empty({4 * C}, fopts);
-    const bool direct = gw_out.has_value() && gw_out->numel() == C;
-    auto gw = direct ? *gw_out : at::empty({C}, fopts);
-    auto gb = direct ? *gb_out : at::empty({C}, fopts);
+    auto ws = at::empty({2 * C}, fopts);
     auto gx = at::empty_like(x);
     auto stream = cur_stream();
-
-    TORCH_CHECK(C % 64 == 0, "BN bwd needs C % 64 == 0, got ", C);
-    const bool xmask = relu && !want_gres && bias.has_value();
-    if (xmask)
-        TORCH_CHECK(bias->scalar_type() == at::kFloat && bias->numel() == C &&
-                    weight.scalar_type() == at::kFloat,
-                    "BN params must be fp32 [C]");
     const float* mask_w = xmask ? weight.data_ptr<float>() : nullptr;
     const float* mask_b = xmask ? bias->data_ptr<float>() : nullptr;
     auto part = at::empty({fda::bn_stats_partial_floats((int)C, rows, dt_of(x))},
@@ -206,8 +319,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_act_bwd(
                              weight.data_ptr<float>(), ws.data_ptr<float>(),
                              gx.data_ptr(),
                              want_gres ? gres.data_ptr() : nullptr,
-                             rows, (int)C, relu, training, dt_of(x), stream,
-                             mask_b);
+                             rows, (int)C, relu, dt_of(x), stream, mask_b);
     return {gx, gw, gb, gres};
 }
 
@@ -231,14 +343,16 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_act_pool_fwd(
     at::Tensor running_var, bool training, double momentum, double eps,
     int64_t KH, int64_t KW, int64_t S, int64_t P,
     c10::optional<at::Tensor> conv_part) {
-    auto [rows, C] = nhwc_rows(x);
+    const char* op = "bn_act_pool_fwd";
+    auto [rows, C] = check_bn_fwd_operands(op, x, weight, bias, running_mean,
+                                           running_var, training, conv_part);
     (void)rows;
     TORCH_CHECK(bn_act_pool_supported(C, dt_of(x) == DT::BF16, KH, KW, S, P),
                 "bn_act_pool: unsupported C=", C, " or pool geometry");
     const int N = (int)x.size(0), H = (int)x.size(2), W = (int)x.size(3);
-    TORCH_CHECK(H + 2 * P >= KH && W + 2 * P >= KW, "pool window > input");
-    const int HO = (int)((H + 2 * P - KH) / S + 1);
-    const int WO = (int)((W + 2 * P - KW) / S + 1);
+    auto [HO, WO] = pool_out_hw(op, H, W, KH, KW, S, P);
+    check_device(op, {x, weight, bias, running_mean, running_var,
+                      conv_part.value_or(at::Tensor())});
     auto [ws, save_mean, save_invstd] =
         bn_fwd_finalize(x, weight, bias, running_mean, running_var, training,
                         momentum, eps, conv_part);
@@ -260,27 +374,30 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_act_pool_bwd(
     c10::optional<at::Tensor> gw_out, c10::optional<at::Tensor> gb_out) {
     // gout: gradient of the POOLED output; returns gx at x's resolution.
     // gw_out/gb_out set: fp32 flat-G slices, written += (direct grad)
+    const char* op = "bn_act_pool_bwd";
     auto [rows, C] = nhwc_rows(x);
     TORCH_CHECK(bn_act_pool_supported(C, dt_of(x) == DT::BF16, KH, KW, S, P),
                 "bn_act_pool: unsupported C=", C, " or pool geometry");
-    TORCH_CHECK(weight.scalar_type() == at::kFloat &&
-                bias.scalar_type() == at::kFloat && bias.numel() == C,
-                "BN params must be fp32 [C]");
+    check_flat(op, "weight", weight, at::kFloat, C);
+    check_flat(op, "bias", bias, at::kFloat, C);
+    check_flat(op, "save_mean", save_mean, at::kFloat, C);
+    check_flat(op, "save_invstd", save_invstd, at::kFloat, C);
     const int N = (int)x.size(0), H = (int)x.size(2), W = (int)x.size(3);
-    const int HO = (int)((H + 2 * P - KH) / S + 1);
-    const int WO = (int)((W + 2 * P - KW) / S + 1);
+    auto [HO, WO] = pool_out_hw(op, H, W, KH, KW, S, P);
     auto gc = gout.contiguous(at::MemoryFormat::ChannelsLast);
-    TORCH_CHECK(gc.scalar_type() == x.scalar_type() && gc.size(0) == N &&
-                gc.size(1) == C && gc.size(2) == HO && gc.size(3) == WO,
+    TORCH_CHECK(gc.scalar_type() == x.scalar_type() && gc.dim() == 4 &&
+                gc.size(0) == N && gc.size(1) == C && gc.size(2) == HO &&
+                gc.size(3) == WO,
                 "bn_act_pool_bwd: gout does not match the pooled shape");
     TORCH_CHECK(idx.scalar_type() == at::kByte && idx.is_contiguous() &&
                 idx.numel() == (int64_t)N * HO * WO * C,
                 "bn_act_pool_bwd: argmax bytes do not match the pooled shape");
+    auto [gw, gb, direct] = bn_bwd_grad_targets(op, x, C, gw_out, gb_out);
+    check_device(op, {x, gc, weight, bias, save_mean, save_invstd, idx, gw,
+                      gb});
+
     auto fopts = x.options().dtype(at::kFloat);
-    auto ws = at::empty({4 * C}, fopts);
-    const bool direct = gw_out.has_value() && gw_out->numel() == C;
-    auto gw = direct ? *gw_out : at::empty({C}, fopts);
-    auto gb = direct ? *gb_out : at::empty({C}, fopts);
+    auto ws = at::empty({2 * C}, fopts);
     auto gx = at::empty_like(x);
     auto stream = cur_stream();
     const int NB = fda::bn_relu_maxpool_bwd_blocks(N, H);
@@ -291,10 +408,10 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_act_pool_bwd(
         weight.data_ptr<float>(), bias.data_ptr<float>(),
         part.data_ptr<float>(), N, H, W, (int)C, HO, WO, (int)KH, (int)KW,
         (int)S, (int)P, dt_of(x), stream);
-    fda::bn_bwd_finalize_from_partials_launch(
-        part.data_ptr<float>(), NB, ws.data_ptr<float>(),
-        gw.data_ptr<float>(), gb.data_ptr<float>(), rows, (int)C, training,
-        direct, stream);
+    fda::bn_bwd_finalize_launch(part.data_ptr<float>(), NB, (int)C, 0,
+                                ws.data_ptr<float>(), gw.data_ptr<float>(),
+                                gb.data_ptr<float>(), rows, (int)C, training,
+                                direct, stream);
     fda::bn_relu_maxpool_bwd_apply_launch(
         gc.data_ptr(), idx.data_ptr<uint8_t>(), x.data_ptr(),
         save_mean.data_ptr<float>(), save_invstd.data_ptr<float>(),
@@ -307,13 +424,13 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_act_pool_bwd(
 std::tuple<at::Tensor, at::Tensor> maxpool_fwd(at::Tensor x, int64_t KH,
                                                int64_t KW, int64_t S,
                                                int64_t P) {
+    const char* op = "maxpool_fwd";
     auto [rows, C] = nhwc_rows(x);
     (void)rows;
-    const int V = dt_of(x) == DT::BF16 ? 8 : 4;
-    TORCH_CHECK(C % V == 0);
+    check_vec_channels(op, x, C);
     const int N = (int)x.size(0), H = (int)x.size(2), W = (int)x.size(3);
-    const int HO = (int)((H + 2 * P - KH) / S + 1);
-    const int WO = (int)((W + 2 * P - KW) / S + 1);
+    auto [HO, WO] = pool_out_hw(op, H, W, KH, KW, S, P);
+    check_device(op, {x});
     auto out = at::empty({N, C, HO, WO},
                          x.options().memory_format(at::MemoryFormat::ChannelsLast));
     auto idx = at::empty({(int64_t)N * HO * WO * C},
@@ -327,9 +444,18 @@ std::tuple<at::Tensor, at::Tensor> maxpool_fwd(at::Tensor x, int64_t KH,
 
 at::Tensor maxpool_bwd(at::Tensor gout, at::Tensor idx, int64_t H, int64_t W,
                        int64_t KH, int64_t KW, int64_t S, int64_t P) {
+    const char* op = "maxpool_bwd";
+    TORCH_CHECK(gout.dim() == 4, op, ": gout must be 4-D");
     auto gc = gout.contiguous(at::MemoryFormat::ChannelsLast);
     const int N = (int)gc.size(0), C = (int)gc.size(1);
-    const int HO = (int)gc.size(2), WO = (int)gc.size(3);
+    check_vec_channels(op, gc, C);
+    auto [HO, WO] = pool_out_hw(op, H, W, KH, KW, S, P);
+    TORCH_CHECK(gc.size(2) == HO && gc.size(3) == WO, op,
+                ": gout is not the pooled shape of a ", H, "x", W, " input");
+    TORCH_CHECK(idx.scalar_type() == at::kByte && idx.is_contiguous() &&
+                idx.numel() == gc.numel(),
+                op, ": argmax bytes do not match the pooled shape");
+    check_device(op, {gc, idx});
     auto gx = at::empty({N, C, (int)H, (int)W},
                         gc.options().memory_format(at::MemoryFormat::ChannelsLast));
     fda::maxpool_bwd_launch(gc.data_ptr(), idx.data_ptr<uint8_t>(),
@@ -339,13 +465,29 @@ at::Tensor maxpool_bwd(at::Tensor gout, at::Tensor idx, int64_t H, int64_t W,
     return gx;
 }
 
-void sgd_step(at::Tensor P, at::Tensor G, at::Tensor M, at::Tensor V,
-              double lr, double mom, double wd, bool nesterov) {
-    TORCH_CHECK(P.is_contiguous() && G.is_contiguous() && V.is_contiguous());
+// Flat optimizer buffers: P/G in the param dtype, the master M (fp32; P
+// itself for fp32 params that have none) and the fp32 state buffers, all
+// contiguous and of P's length. Returns has_master; the device check is the
+// caller's.
+bool check_optimizer_operands(const char* op, const at::Tensor& P,
+                              const at::Tensor& G, const at::Tensor& M,
+                              std::initializer_list<at::Tensor> state) {
     const int vw = dt_of(P) == DT::BF16 ? 8 : 4;
-    TORCH_CHECK(P.numel() % vw == 0, "flat buffer must be padded to ", vw);
+    const int64_t n = P.numel();
+    TORCH_CHECK(n % vw == 0, "flat buffer must be padded to ", vw);
+    check_flat(op, "P", P, P.scalar_type(), n);
+    check_flat(op, "G", G, P.scalar_type(), n);
+    check_flat(op, "M", M, at::kFloat, n);
+    for (const auto& t : state) check_flat(op, "state", t, at::kFloat, n);
     const bool has_master = M.data_ptr() != P.data_ptr();
     if (dt_of(P) == DT::BF16) TORCH_CHECK(has_master, "bf16 params need fp32 master");
+    return has_master;
+}
+
+void sgd_step(at::Tensor P, at::Tensor G, at::Tensor M, at::Tensor V,
+              double lr, double mom, double wd, bool nesterov) {
+    const bool has_master = check_optimizer_operands("sgd_step", P, G, M, {V});
+    check_device("sgd_step", {P, G, M, V});
     fda::sgd_step_launch(P.data_ptr(), G.data_ptr(), M.data_ptr<float>(),
                          V.data_ptr<float>(), P.numel(), (float)lr, (float)mom,
                          (float)wd, nesterov, has_master, dt_of(P),
@@ -355,10 +497,9 @@ void sgd_step(at::Tensor P, at::Tensor G, at::Tensor M, at::Tensor V,
 void adam_step(at::Tensor P, at::Tensor G, at::Tensor M, at::Tensor V,
                at::Tensor S, double lr, double b1, double b2, double eps,
                double wd, double bc1, double bc2) {
-    const int vw = dt_of(P) == DT::BF16 ? 8 : 4;
-    TORCH_CHECK(P.numel() % vw == 0, "flat buffer must be padded to ", vw);
-    const bool has_master = M.data_ptr() != P.data_ptr();
-    if (dt_of(P) == DT::BF16) TORCH_CHECK(has_master, "bf16 params need fp32 master");
+    const bool has_master =
+        check_optimizer_operands("adam_step", P, G, M, {V, S});
+    check_device("adam_step", {P, G, M, V, S});
     fda::adam_step_launch(P.data_ptr(), G.data_ptr(), M.data_ptr<float>(),
                           V.data_ptr<float>(), S.data_ptr<float>(), P.numel(),
                           (float)lr, (float)b1, (float)b2, (float)eps,
@@ -399,7 +540,7 @@ static void check_conv_operands(const at::Tensor& act, const at::Tensor& other,
 }
 
 // forward, optionally with per-m-tile BN partials [tiles][2][K] (sum/sumsq
-// of the rounded output) that feed bn_finalize_from_partials; the partials
+// of the rounded output) that feed bn_fwd_finalize_launch; the partials
 // tensor is undefined when want_stats is false.
 static std::tuple<at::Tensor, at::Tensor> conv_igemm_fwd_impl(
     const at::Tensor& x, const at::Tensor& w, int64_t sy, int64_t sx,
@@ -536,52 +677,76 @@ at::Tensor conv_igemm_wgrad(at::Tensor dy, at::Tensor x,
 }
 
 
-at::Tensor conv_stem_fwd(at::Tensor x8, at::Tensor wpad, int64_t R,
-                         int64_t sy, int64_t sx, int64_t P, int64_t Q) {
-    // x8: [N,8,Hp,Wp] channels_last bf16 (spatially pre-padded, channels
-    // 3..7 zero); wpad: [K][R][64] bf16 (s==7 and c>=3 taps zero).
-    TORCH_CHECK(x8.is_cuda() && wpad.is_cuda());
-    TORCH_CHECK(x8.scalar_type() == at::kBFloat16 &&
-                x8.is_contiguous(at::MemoryFormat::ChannelsLast));
-    TORCH_CHECK(x8.size(1) == 8);
-    TORCH_CHECK(wpad.is_contiguous() && wpad.scalar_type() == at::kBFloat16);
-    const int N = (int)x8.size(0), Hp = (int)x8.size(2), Wp = (int)x8.size(3);
+// Operand checks shared by the stem entry points. x8: [N,8,Hp,Wp]
+// channels_last bf16 (spatially pre-padded, channels 3..7 zero). Output
+// pixel (p, q) reads filter row r from input row p*sy + r, columns
+// q*sx .. q*sx + 7, which must stay inside the padded image.
+static void check_stem_geometry(const char* op, const at::Tensor& x8,
+                                int64_t K, int64_t R, int64_t sy, int64_t sx,
+                                int64_t P, int64_t Q) {
+    TORCH_CHECK(x8.scalar_type() == at::kBFloat16 && x8.dim() == 4 &&
+                    x8.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                    x8.size(1) == 8,
+                op, ": x8 must be [N,8,Hp,Wp] channels_last bf16");
+    TORCH_CHECK(K >= 64 && K % 64 == 0, op, ": K must be a multiple of 64");
+    TORCH_CHECK(R >= 1 && sy >= 1 && sx >= 1 && P >= 1 && Q >= 1 &&
+                    (P - 1) * sy + R <= x8.size(2) &&
+                    (Q - 1) * sx + 8 <= x8.size(3),
+                op, ": output ", P, "x", Q, " reads outside the padded ",
+                x8.size(2), "x", x8.size(3), " input");
+}
+
+// wpad: [K][R][64] bf16 (s==7 and c>=3 taps zero). With want_stats also the
+// per-m-tile BN partials [tiles][2][K]; undefined otherwise.
+static std::tuple<at::Tensor, at::Tensor> conv_stem_fwd_impl(
+    const at::Tensor& x8, const at::Tensor& wpad, int64_t R, int64_t sy,
+    int64_t sx, int64_t P, int64_t Q, bool want_stats) {
+    const char* op = "conv_stem_fwd";
+    TORCH_CHECK(wpad.dim() == 3 && wpad.is_contiguous() &&
+                    wpad.scalar_type() == at::kBFloat16 &&
+                    wpad.size(1) == R && wpad.size(2) == 64,
+                op, ": wpad must be contiguous bf16 [K][R][64]");
     const int K = (int)wpad.size(0);
-    TORCH_CHECK(K % 64 == 0 && wpad.size(1) == R && wpad.size(2) == 64);
+    check_stem_geometry(op, x8, K, R, sy, sx, P, Q);
+    check_device(op, {x8, wpad});
+    const int N = (int)x8.size(0), Hp = (int)x8.size(2), Wp = (int)x8.size(3);
     auto y = at::empty({N, K, P, Q},
                        x8.options().memory_format(at::MemoryFormat::ChannelsLast));
+    at::Tensor part;
+    if (want_stats) {
+        const long M = (long)N * P * Q;
+        part = at::empty({(M + 256 - 1) / 256, 2, K},
+                         x8.options().dtype(at::kFloat));
+    }
     fda::conv_stem_fwd_launch(x8.data_ptr(), wpad.data_ptr(), y.data_ptr(),
                               N, Hp, Wp, K, (int)P, (int)Q, (int)R, (int)sy,
-                              (int)sx, cur_stream());
-    return y;
+                              (int)sx, cur_stream(),
+                              want_stats ? part.data_ptr<float>() : nullptr);
+    return {y, part};
+}
+
+at::Tensor conv_stem_fwd(at::Tensor x8, at::Tensor wpad, int64_t R,
+                         int64_t sy, int64_t sx, int64_t P, int64_t Q) {
+    return std::get<0>(conv_stem_fwd_impl(x8, wpad, R, sy, sx, P, Q, false));
 }
 
 std::tuple<at::Tensor, at::Tensor> conv_stem_fwd_stats(
     at::Tensor x8, at::Tensor wpad, int64_t R, int64_t sy, int64_t sx,
     int64_t P, int64_t Q) {
-    TORCH_CHECK(x8.size(1) == 8 &&
-                x8.is_contiguous(at::MemoryFormat::ChannelsLast));
-    const int N = (int)x8.size(0), Hp = (int)x8.size(2), Wp = (int)x8.size(3);
-    const int K = (int)wpad.size(0);
-    const long M = (long)N * P * Q;
-    const long mtiles = (M + 256 - 1) / 256;
-    auto y = at::empty({N, K, P, Q},
-                       x8.options().memory_format(at::MemoryFormat::ChannelsLast));
-    auto part = at::empty({mtiles, 2, K}, x8.options().dtype(at::kFloat));
-    fda::conv_stem_fwd_launch(x8.data_ptr(), wpad.data_ptr(), y.data_ptr(),
-                              N, Hp, Wp, K, (int)P, (int)Q, (int)R, (int)sy,
-                              (int)sx, cur_stream(), part.data_ptr<float>());
-    return {y, part};
+    return conv_stem_fwd_impl(x8, wpad, R, sy, sx, P, Q, true);
 }
 
 at::Tensor conv_stem_wgrad(at::Tensor dy, at::Tensor x8, int64_t R,
                            int64_t sy, int64_t sx) {
-    TORCH_CHECK(dy.scalar_type() == at::kBFloat16 &&
-                dy.is_contiguous(at::MemoryFormat::ChannelsLast));
-    TORCH_CHECK(x8.scalar_type() == at::kBFloat16 &&
-                x8.is_contiguous(at::MemoryFormat::ChannelsLast));
-    const int N = (int)x8.size(0), Hp = (int)x8.size(2), Wp = (int)x8.size(3);
+    const char* op = "conv_stem_wgrad";
+    TORCH_CHECK(dy.scalar_type() == at::kBFloat16 && dy.dim() == 4 &&
+                    dy.is_contiguous(at::MemoryFormat::ChannelsLast),
+                op, ": dy must be 4-D channels_last bf16");
     const int K = (int)dy.size(1), P = (int)dy.size(2), Q = (int)dy.size(3);
+    check_stem_geometry(op, x8, K, R, sy, sx, P, Q);
+    TORCH_CHECK(dy.size(0) == x8.size(0), op, ": batch size mismatch");
+    check_device(op, {dy, x8});
+    const int N = (int)x8.size(0), Hp = (int)x8.size(2), Wp = (int)x8.size(3);
     auto ws = at::zeros({K, R * 64}, x8.options().dtype(at::kFloat));
     fda::conv_stem_wgrad_launch(dy.data_ptr(), x8.data_ptr(),
                                 ws.data_ptr<float>(), N, Hp, Wp, K, P, Q,
@@ -596,6 +761,7 @@ at::Tensor pad_rows_bf16(at::Tensor src, int64_t ldl) {
     const long M = src.size(0);
     const int C = (int)src.size(1);
     TORCH_CHECK(C % 8 == 0 && ldl % 8 == 0 && ldl >= C);
+    check_device("pad_rows_bf16", {src});
     auto dst = at::empty({M, ldl}, src.options());
     fda::pad_rows_bf16_launch(dst.data_ptr(), src.data_ptr(), M, C, (int)ldl,
                               cur_stream());
@@ -606,6 +772,14 @@ void pad_rows_bf16_into(at::Tensor dst, at::Tensor src) {
     TORCH_CHECK(dst.dim() == 2 && src.dim() == 2);
     TORCH_CHECK(dst.is_contiguous() && src.is_contiguous());
     TORCH_CHECK(dst.size(0) == src.size(0));
+    TORCH_CHECK(dst.scalar_type() == at::kBFloat16 &&
+                    src.scalar_type() == at::kBFloat16,
+                "pad_rows_bf16_into: bf16 only");
+    TORCH_CHECK(src.size(1) % 8 == 0 && dst.size(1) % 8 == 0 &&
+                    src.size(1) <= dst.size(1),
+                "pad_rows_bf16_into: row lengths must be multiples of 8 "
+                "with src's <= dst's");
+    check_device("pad_rows_bf16_into", {dst, src});
     fda::pad_rows_bf16_launch(dst.data_ptr(), src.data_ptr(), src.size(0),
                               (int)src.size(1), (int)dst.size(1),
                               cur_stream());
@@ -616,6 +790,8 @@ void bias_add_rows_bf16(at::Tensor y, at::Tensor bias) {
                 y.scalar_type() == at::kBFloat16);
     TORCH_CHECK(bias.numel() == y.size(1) && bias.is_contiguous() &&
                 bias.scalar_type() == at::kBFloat16);
+    TORCH_CHECK(y.size(1) % 8 == 0, "bias_add_rows_bf16: row length % 8");
+    check_device("bias_add_rows_bf16", {y, bias});
     fda::bias_add_rows_bf16_launch(y.data_ptr(), bias.data_ptr(), y.size(0),
                                    (int)y.size(1), cur_stream());
 }
@@ -626,6 +802,7 @@ void colsum_accum_bf16(at::Tensor g, at::Tensor dy) {
                 dy.scalar_type() == at::kBFloat16);
     TORCH_CHECK(g.is_contiguous() && g.scalar_type() == at::kBFloat16);
     TORCH_CHECK(g.numel() <= dy.size(1));
+    check_device("colsum_accum_bf16", {g, dy});
     fda::colsum_accum_bf16_launch(g.data_ptr(), dy.data_ptr(), dy.size(0),
                                   (int)dy.size(1), (int)g.numel(),
                                   cur_stream());
@@ -634,9 +811,11 @@ void colsum_accum_bf16(at::Tensor g, at::Tensor dy) {
 void grad_accum_batch(at::Tensor g_ptrs, at::Tensor ws_ptrs, at::Tensor ns,
                       int64_t max_n) {
     // device int64 tensors: g/ws addresses and lengths per slice
-    TORCH_CHECK(g_ptrs.is_cuda() && g_ptrs.scalar_type() == at::kLong);
-    TORCH_CHECK(ws_ptrs.numel() == g_ptrs.numel() &&
-                ns.numel() == g_ptrs.numel());
+    const int64_t n = g_ptrs.numel();
+    check_flat("grad_accum_batch", "g_ptrs", g_ptrs, at::kLong, n);
+    check_flat("grad_accum_batch", "ws_ptrs", ws_ptrs, at::kLong, n);
+    check_flat("grad_accum_batch", "ns", ns, at::kLong, n);
+    check_device("grad_accum_batch", {g_ptrs, ws_ptrs, ns});
     fda::grad_accum_batch_launch(g_ptrs.data_ptr<int64_t>(),
                                  ws_ptrs.data_ptr<int64_t>(),
                                  ns.data_ptr<int64_t>(),
@@ -647,6 +826,7 @@ void grad_accum_bf16(at::Tensor g, at::Tensor ws) {
     TORCH_CHECK(g.scalar_type() == at::kBFloat16 && g.is_contiguous());
     TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous());
     TORCH_CHECK(g.numel() == ws.numel());
+    check_device("grad_accum_bf16", {g, ws});
     fda::grad_accum_bf16_launch(g.data_ptr(), ws.data_ptr<float>(),
                                 (long)g.numel(), cur_stream());
 }
@@ -654,8 +834,14 @@ void grad_accum_bf16(at::Tensor g, at::Tensor ws) {
 void wt_transpose_batch(at::Tensor src_ptrs, at::Tensor dst_ptrs,
                         at::Tensor Ks, at::Tensor RCs, at::Tensor tile_counts,
                         int64_t max_tiles) {
-    TORCH_CHECK(src_ptrs.is_cuda() && src_ptrs.scalar_type() == at::kLong);
+    const char* op = "wt_transpose_batch";
     const int n = (int)src_ptrs.numel();
+    check_flat(op, "src_ptrs", src_ptrs, at::kLong, n);
+    check_flat(op, "dst_ptrs", dst_ptrs, at::kLong, n);
+    check_flat(op, "Ks", Ks, at::kInt, n);
+    check_flat(op, "RCs", RCs, at::kInt, n);
+    check_flat(op, "tile_counts", tile_counts, at::kInt, n);
+    check_device(op, {src_ptrs, dst_ptrs, Ks, RCs, tile_counts});
     fda::wt_transpose_launch(src_ptrs.data_ptr<int64_t>(),
                              dst_ptrs.data_ptr<int64_t>(),
                              Ks.data_ptr<int>(), RCs.data_ptr<int>(),
@@ -665,6 +851,9 @@ void wt_transpose_batch(at::Tensor src_ptrs, at::Tensor dst_ptrs,
 
 at::Tensor gap_fwd(at::Tensor x) {
     auto [rows, C] = nhwc_rows(x);
+    check_vec_channels("gap_fwd", x, C);
+    TORCH_CHECK(x.size(0) >= 1, "gap_fwd: empty batch");
+    check_device("gap_fwd", {x});
     const int N = (int)x.size(0);
     const int HW = (int)(rows / N);
     auto y = at::empty({N, C}, x.options());
@@ -676,6 +865,9 @@ at::Tensor gap_fwd(at::Tensor x) {
 at::Tensor gap_bwd(at::Tensor gy, int64_t H, int64_t W) {
     TORCH_CHECK(gy.dim() == 2 && gy.is_contiguous());
     const int N = (int)gy.size(0), C = (int)gy.size(1);
+    check_vec_channels("gap_bwd", gy, C);
+    TORCH_CHECK(H >= 1 && W >= 1, "gap_bwd: H and W must be positive");
+    check_device("gap_bwd", {gy});
     auto gx = at::empty({N, C, H, W},
                         gy.options().memory_format(at::MemoryFormat::ChannelsLast));
     fda::gap_bwd_launch(gy.data_ptr(), gx.data_ptr(), N, (int)(H * W), C,

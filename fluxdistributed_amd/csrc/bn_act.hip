@@ -29,9 +29,9 @@ __global__ void bn_stats_kernel(const T* __restrict__ x,
     const int sub_r = threadIdx.x / tpr;
     const int c0 = c_base + lane_c * V;
 
-    float s[V], q[V];
+    ChanAcc<V> s, q;
     #pragma unroll
-    for (int k = 0; k < V; ++k) s[k] = q[k] = 0.f;
+    for (int k = 0; k < V; ++k) s.v[k] = q.v[k] = 0.f;
 
     // 2 independent row streams per iteration for memory-level parallelism
     const int64_t stride = (int64_t)gridDim.x * rpb;
@@ -44,41 +44,20 @@ __global__ void bn_stats_kernel(const T* __restrict__ x,
         #pragma unroll
         for (int k = 0; k < V; ++k) {
             float v = load_f32(xv + k);
-            s[k] += v;
-            q[k] += v * v;
+            s.v[k] += v;
+            q.v[k] += v * v;
         }
         if (second) {
             #pragma unroll
             for (int k = 0; k < V; ++k) {
                 float v = load_f32(xw + k);
-                s[k] += v;
-                q[k] += v * v;
+                s.v[k] += v;
+                q.v[k] += v * v;
             }
         }
     }
-    // reduce over the rpb row-groups, one array at a time
-    float* out = part + (int64_t)blockIdx.x * 2 * chunkC;
-    #pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        float* loc = pass == 0 ? s : q;
-        #pragma unroll
-        for (int k = 0; k < V; ++k) smem[threadIdx.x * V + k] = loc[k];
-        __syncthreads();
-        if (sub_r == 0) {
-            float acc[V];
-            #pragma unroll
-            for (int k = 0; k < V; ++k) acc[k] = 0.f;
-            for (int rr = 0; rr < rpb; ++rr) {
-                const float* src = smem + (rr * tpr + lane_c) * V;
-                #pragma unroll
-                for (int k = 0; k < V; ++k) acc[k] += src[k];
-            }
-            #pragma unroll
-            for (int k = 0; k < V; ++k)
-                out[pass * chunkC + lane_c * V + k] = acc[k];
-        }
-        __syncthreads();
-    }
+    block_fold_rows<V>(s, q, smem, part + (int64_t)blockIdx.x * 2 * chunkC,
+                       tpr, chunkC);
 }
 
 // Fold part[NB][2*chunkC] into two per-channel totals (s, q), then run a
@@ -167,8 +146,8 @@ __global__ void bn_fwd_reduce_finalize_kernel(
         save_mean[c] = mean;
         save_invstd[c] = invstd;
         const float scale = bn_scale_of(weight[c], invstd);
-        ws[2 * C + c] = scale;
-        ws[3 * C + c] = bn_shift_of(bias[c], mean, scale);
+        ws[c] = scale;
+        ws[C + c] = bn_shift_of(bias[c], mean, scale);
     });
 }
 
@@ -181,8 +160,8 @@ __global__ void bn_bwd_reduce_finalize_kernel(
         gb[c] = accum ? gb[c] + t.s : t.s;  // sum_g
         gw[c] = accum ? gw[c] + t.q : t.q;  // sum_g_xhat
         const float inv_m = training ? 1.f / (float)rows : 0.f;
-        ws[2 * C + c] = t.s * inv_m;       // k1
-        ws[3 * C + c] = t.q * inv_m;       // k2
+        ws[c] = t.s * inv_m;       // k1
+        ws[C + c] = t.q * inv_m;   // k2
     });
 }
 
@@ -202,8 +181,8 @@ __global__ void bn_eval_finalize_kernel(float* __restrict__ ws,
     save_mean[c] = mean;
     save_invstd[c] = invstd;
     const float scale = bn_scale_of(weight[c], invstd);
-    ws[2 * C + c] = scale;
-    ws[3 * C + c] = bn_shift_of(bias[c], mean, scale);
+    ws[c] = scale;
+    ws[C + c] = bn_shift_of(bias[c], mean, scale);
 }
 
 template <typename T, int V, bool RELU, bool RES>
@@ -255,12 +234,13 @@ __global__ void bn_bwd_stats_kernel(const T* __restrict__ gout,
     const int sub_r = threadIdx.x / tpr;
     const int c0 = c_base + lane_c * V;
 
-    float mu[V], is[V], sg[V], sgx[V], sc[V], sh[V];
+    float mu[V], is[V], sc[V], sh[V];
+    ChanAcc<V> sg, sgx;
     #pragma unroll
     for (int k = 0; k < V; ++k) {
         mu[k] = mean[c0 + k];
         is[k] = invstd[c0 + k];
-        sg[k] = sgx[k] = 0.f;
+        sg.v[k] = sgx.v[k] = 0.f;
         if constexpr (XMASK) {
             sc[k] = bn_scale_of(weight[c0 + k], is[k]);
             sh[k] = bn_shift_of(bias[c0 + k], mu[k], sc[k]);
@@ -281,32 +261,12 @@ __global__ void bn_bwd_stats_kernel(const T* __restrict__ gout,
             else if constexpr (RELU)
                 g = load_f32(ov + k) > 0.f ? g : 0.f;
             const float xhat = (load_f32(xv + k) - mu[k]) * is[k];
-            sg[k] += g;
-            sgx[k] += g * xhat;
+            sg.v[k] += g;
+            sgx.v[k] += g * xhat;
         }
     }
-    float* outp = part + (int64_t)blockIdx.x * 2 * chunkC;
-    #pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        float* loc = pass == 0 ? sg : sgx;
-        #pragma unroll
-        for (int k = 0; k < V; ++k) smem[threadIdx.x * V + k] = loc[k];
-        __syncthreads();
-        if (sub_r == 0) {
-            float acc[V];
-            #pragma unroll
-            for (int k = 0; k < V; ++k) acc[k] = 0.f;
-            for (int rr = 0; rr < rpb; ++rr) {
-                const float* src = smem + (rr * tpr + lane_c) * V;
-                #pragma unroll
-                for (int k = 0; k < V; ++k) acc[k] += src[k];
-            }
-            #pragma unroll
-            for (int k = 0; k < V; ++k)
-                outp[pass * chunkC + lane_c * V + k] = acc[k];
-        }
-        __syncthreads();
-    }
+    block_fold_rows<V>(sg, sgx, smem,
+                       part + (int64_t)blockIdx.x * 2 * chunkC, tpr, chunkC);
 }
 
 template <typename T, int V, bool RELU, bool XMASK = false>
@@ -347,8 +307,8 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ gout,
             }
             store_f32(mv + k, g);
             const float xhat = (load_f32(xv + k) - mean[c]) * is;
-            const float r = (g - k1[c] - xhat * k2[c]) * weight[c] * is;
-            store_f32(rv_ + k, r);
+            store_f32(rv_ + k,
+                      bn_bwd_dx(g, xhat, k1[c], k2[c], weight[c], is));
         }
         ((uint4*)gx)[i] = *(uint4*)rv_;
         if (gres != nullptr) ((uint4*)gres)[i] = *(uint4*)mv;
@@ -387,28 +347,35 @@ void bn_stats_launch(const void* x, float* ws, float* part,
     for (int ch = 0; ch < nchunks; ++ch) {
         const int c_base = ch * chunkC;
         const int cc = (C - c_base) < chunkC ? (C - c_base) : chunkC;
-        if (dt == DT::BF16)
-            hipLaunchKernelGGL((bn_stats_kernel<unsigned short, 8>), dim3(grid),
-                               dim3(256), shmem, s, (const unsigned short*)x,
-                               part, rows, C, c_base, cc);
-        else
-            hipLaunchKernelGGL((bn_stats_kernel<float, 4>), dim3(grid),
-                               dim3(256), shmem, s, (const float*)x, part,
-                               rows, C, c_base, cc);
-        hipLaunchKernelGGL(bn_fwd_reduce_finalize_kernel, dim3(cc / FIN_CH),
-                           dim3(256), 0, s, part, weight, bias, running_mean,
-                           running_var, save_mean, save_invstd, ws, grid, cc,
-                           c_base, C, rows, momentum, eps);
+        dispatch_dtype(dt, [&](auto t, auto v) {
+            using T = decltype(t);
+            constexpr int V = decltype(v)::value;
+            hipLaunchKernelGGL((bn_stats_kernel<T, V>), dim3(grid), dim3(256),
+                               shmem, s, (const T*)x, part, rows, C, c_base,
+                               cc);
+        });
+        bn_fwd_finalize_launch(part, grid, cc, c_base, weight, bias,
+                               running_mean, running_var, save_mean,
+                               save_invstd, ws, rows, C, momentum, eps, s);
     }
 }
 
-void bn_finalize_launch(float* ws, const float* weight, const float* bias,
-                        float* running_mean, float* running_var,
-                        float* save_mean, float* save_invstd, int64_t rows,
-                        int C, bool training, float momentum, float eps,
-                        hipStream_t s) {
-    // training path is fused into bn_stats_launch; this is eval-only
-    (void)rows; (void)training; (void)momentum;
+void bn_fwd_finalize_launch(const float* part, int NB, int chunkC, int c_base,
+                            const float* weight, const float* bias, float* rm,
+                            float* rv, float* save_mean, float* save_invstd,
+                            float* ws, int64_t rows, int C, float momentum,
+                            float eps, hipStream_t s) {
+    hipLaunchKernelGGL(bn_fwd_reduce_finalize_kernel, dim3(chunkC / FIN_CH),
+                       dim3(256), 0, s, part, weight, bias, rm, rv, save_mean,
+                       save_invstd, ws, NB, chunkC, c_base, C, rows, momentum,
+                       eps);
+}
+
+void bn_eval_finalize_launch(float* ws, const float* weight,
+                             const float* bias, const float* running_mean,
+                             const float* running_var, float* save_mean,
+                             float* save_invstd, int C, float eps,
+                             hipStream_t s) {
     hipLaunchKernelGGL(bn_eval_finalize_kernel, dim3((C + 255) / 256),
                        dim3(256), 0, s, ws, weight, bias, running_mean,
                        running_var, save_mean, save_invstd, C, eps);
@@ -417,24 +384,21 @@ void bn_finalize_launch(float* ws, const float* weight, const float* bias,
 void bn_apply_launch(const void* x, const void* residual, void* out,
                      const float* ws, int64_t rows, int C, bool relu, DT dt,
                      hipStream_t s) {
-    const int V = dt == DT::BF16 ? 8 : 4;
-    const int64_t nvec = rows * C / V;
-    int64_t blocks = (nvec + 255) / 256;
-    const int grid = (int)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks));
-    const float* scale = ws + 2 * C;
-    const float* shift = ws + 3 * C;
-    #define FDA_APPLY(T, VW, RELU_, RES_)                                       \
-        hipLaunchKernelGGL((bn_apply_kernel<T, VW, RELU_, RES_>), dim3(grid),   \
-                           dim3(256), 0, s, (const T*)x, (const T*)residual,    \
-                           (T*)out, scale, shift, nvec, C)
-    if (dt == DT::BF16) {
-        if (relu) { if (residual) FDA_APPLY(unsigned short, 8, true, true); else FDA_APPLY(unsigned short, 8, true, false); }
-        else      { if (residual) FDA_APPLY(unsigned short, 8, false, true); else FDA_APPLY(unsigned short, 8, false, false); }
-    } else {
-        if (relu) { if (residual) FDA_APPLY(float, 4, true, true); else FDA_APPLY(float, 4, true, false); }
-        else      { if (residual) FDA_APPLY(float, 4, false, true); else FDA_APPLY(float, 4, false, false); }
-    }
-    #undef FDA_APPLY
+    const float* scale = ws;
+    const float* shift = ws + C;
+    dispatch_dtype(dt, [&](auto t, auto v) {
+        using T = decltype(t);
+        constexpr int V = decltype(v)::value;
+        const int64_t nvec = rows * C / V;
+        dispatch_flag(relu, [&](auto RELU) {
+            dispatch_flag(residual != nullptr, [&](auto RES) {
+                hipLaunchKernelGGL(
+                    (bn_apply_kernel<T, V, RELU.value, RES.value>),
+                    dim3(grid_1d(nvec, 4096)), dim3(256), 0, s, (const T*)x,
+                    (const T*)residual, (T*)out, scale, shift, nvec, C);
+            });
+        });
+    });
 }
 
 void bn_bwd_stats_launch(const void* gout, const void* x, const void* out,
@@ -451,27 +415,31 @@ void bn_bwd_stats_launch(const void* gout, const void* x, const void* out,
     for (int ch = 0; ch < nchunks; ++ch) {
         const int c_base = ch * chunkC;
         const int cc = (C - c_base) < chunkC ? (C - c_base) : chunkC;
-        #define FDA_BSTATS(T, VW, RELU_, XM_)                                   \
-            hipLaunchKernelGGL((bn_bwd_stats_kernel<T, VW, RELU_, XM_>),        \
-                               dim3(grid), dim3(256), shmem, s,                 \
-                               (const T*)gout, (const T*)x, (const T*)out,      \
-                               save_mean, save_invstd, weight, bias, part,      \
-                               rows, C, c_base, cc)
-        if (dt == DT::BF16) {
-            if (xmask) FDA_BSTATS(unsigned short, 8, true, true);
-            else if (relu) FDA_BSTATS(unsigned short, 8, true, false);
-            else FDA_BSTATS(unsigned short, 8, false, false);
-        } else {
-            if (xmask) FDA_BSTATS(float, 4, true, true);
-            else if (relu) FDA_BSTATS(float, 4, true, false);
-            else FDA_BSTATS(float, 4, false, false);
-        }
-        #undef FDA_BSTATS
-        hipLaunchKernelGGL(bn_bwd_reduce_finalize_kernel, dim3(cc / FIN_CH),
-                           dim3(256), 0, s, part, ws, gw, gb, grid, cc,
-                           c_base, C, rows, training ? 1 : 0,
-                           accum_g ? 1 : 0);
+        dispatch_dtype(dt, [&](auto t, auto v) {
+            using T = decltype(t);
+            constexpr int V = decltype(v)::value;
+            auto launch = [&](auto RELU, auto XM) {
+                hipLaunchKernelGGL(
+                    (bn_bwd_stats_kernel<T, V, RELU.value, XM.value>),
+                    dim3(grid), dim3(256), shmem, s, (const T*)gout,
+                    (const T*)x, (const T*)out, save_mean, save_invstd,
+                    weight, bias, part, rows, C, c_base, cc);
+            };
+            // XMASK exists only with RELU
+            if (!relu) launch(std::false_type{}, std::false_type{});
+            else dispatch_flag(xmask, [&](auto XM) { launch(std::true_type{}, XM); });
+        });
+        bn_bwd_finalize_launch(part, grid, cc, c_base, ws, gw, gb, rows, C,
+                               training, accum_g, s);
     }
+}
+
+void bn_bwd_finalize_launch(const float* part, int NB, int chunkC, int c_base,
+                            float* ws, float* gw, float* gb, int64_t rows,
+                            int C, bool training, bool accum_g, hipStream_t s) {
+    hipLaunchKernelGGL(bn_bwd_reduce_finalize_kernel, dim3(chunkC / FIN_CH),
+                       dim3(256), 0, s, part, ws, gw, gb, NB, chunkC, c_base,
+                       C, rows, training ? 1 : 0, accum_g ? 1 : 0);
 }
 
 // Pre-fold for conv-epilogue partials: mtiles can reach ~4700 for the
@@ -531,58 +499,30 @@ void bn_partial_prefold_launch(const float* part, float* out, int NB,
                        part, out, NB, NB2, chunkC);
 }
 
-void bn_finalize_from_partials_launch(
-    const float* part, int NB, const float* weight, const float* bias,
-    float* rm, float* rv, float* save_mean, float* save_invstd, float* ws,
-    int64_t rows, int C, float momentum, float eps, hipStream_t s) {
-    // partials produced by the conv epilogue ([NB][2][C], single chunk);
-    // same reduce+finalize kernel the in-house stats pass feeds.
-    hipLaunchKernelGGL(bn_fwd_reduce_finalize_kernel, dim3(C / FIN_CH),
-                       dim3(256), 0, s, part, weight, bias, rm, rv,
-                       save_mean, save_invstd, ws, NB, C, 0, C, rows,
-                       momentum, eps);
-}
-
-void bn_bwd_finalize_from_partials_launch(const float* part, int NB,
-                                          float* ws, float* gw, float* gb,
-                                          int64_t rows, int C, bool training,
-                                          bool accum_g, hipStream_t s) {
-    // partials produced by the fused BN+ReLU+pool backward stats pass
-    // ([NB][2][C], single chunk); same kernel bn_bwd_stats_launch feeds
-    hipLaunchKernelGGL(bn_bwd_reduce_finalize_kernel, dim3(C / FIN_CH),
-                       dim3(256), 0, s, part, ws, gw, gb, NB, C, 0, C, rows,
-                       training ? 1 : 0, accum_g ? 1 : 0);
-}
-
 void bn_bwd_apply_launch(const void* gout, const void* x, const void* out,
                          const float* save_mean, const float* save_invstd,
                          const float* weight, const float* ws, void* gx,
-                         void* gres, int64_t rows, int C, bool relu,
-                         bool /*training*/, DT dt, hipStream_t s,
-                         const float* bias) {
+                         void* gres, int64_t rows, int C, bool relu, DT dt,
+                         hipStream_t s, const float* bias) {
     // bias given (non-residual ReLU BN): mask from x, `out` unread
     const bool xmask = relu && bias != nullptr && gres == nullptr;
-    const int V = dt == DT::BF16 ? 8 : 4;
-    const int64_t nvec = rows * C / V;
-    int64_t blocks = (nvec + 255) / 256;
-    const int grid = (int)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks));
-    const float* k1 = ws + 2 * C;
-    const float* k2 = ws + 3 * C;
-    #define FDA_BAPPLY(T, VW, RELU_, XM_)                                       \
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<T, VW, RELU_, XM_>),            \
-                           dim3(grid), dim3(256), 0, s, (const T*)gout,         \
-                           (const T*)x, (const T*)out, save_mean, save_invstd,  \
-                           weight, bias, k1, k2, (T*)gx, (T*)gres, nvec, C)
-    if (dt == DT::BF16) {
-        if (xmask) FDA_BAPPLY(unsigned short, 8, true, true);
-        else if (relu) FDA_BAPPLY(unsigned short, 8, true, false);
-        else FDA_BAPPLY(unsigned short, 8, false, false);
-    } else {
-        if (xmask) FDA_BAPPLY(float, 4, true, true);
-        else if (relu) FDA_BAPPLY(float, 4, true, false);
-        else FDA_BAPPLY(float, 4, false, false);
-    }
-    #undef FDA_BAPPLY
+    const float* k1 = ws;
+    const float* k2 = ws + C;
+    dispatch_dtype(dt, [&](auto t, auto v) {
+        using T = decltype(t);
+        constexpr int V = decltype(v)::value;
+        const int64_t nvec = rows * C / V;
+        auto launch = [&](auto RELU, auto XM) {
+            hipLaunchKernelGGL(
+                (bn_bwd_apply_kernel<T, V, RELU.value, XM.value>),
+                dim3(grid_1d(nvec, 4096)), dim3(256), 0, s, (const T*)gout,
+                (const T*)x, (const T*)out, save_mean, save_invstd, weight,
+                bias, k1, k2, (T*)gx, (T*)gres, nvec, C);
+        };
+        // XMASK exists only with RELU
+        if (!relu) launch(std::false_type{}, std::false_type{});
+        else dispatch_flag(xmask, [&](auto XM) { launch(std::true_type{}, XM); });
+    });
 }
 
 }  // namespace fda

@@ -68,14 +68,12 @@ void ce_fwd_launch(const void* logits, const int64_t* target, float* loss,
                    hipStream_t s) {
     dim3 grid(N < 2048 ? N : 2048), block(256);
     size_t shmem = (C + 16) * sizeof(float);
-    if (dt == DT::BF16)
-        hipLaunchKernelGGL(ce_fwd_kernel<unsigned short>, grid, block, shmem, s,
-                           (const unsigned short*)logits, target, loss,
-                           (unsigned short*)dlogits, N, C, ldl);
-    else
-        hipLaunchKernelGGL(ce_fwd_kernel<float>, grid, block, shmem, s,
-                           (const float*)logits, target, loss, (float*)dlogits,
-                           N, C, ldl);
+    dispatch_dtype(dt, [&](auto t, auto) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(ce_fwd_kernel<T>, grid, block, shmem, s,
+                           (const T*)logits, target, loss, (T*)dlogits, N, C,
+                           ldl);
+    });
 }
 
 // --------------------------------------------------------------------------
@@ -124,35 +122,26 @@ __global__ void add_relu_bwd_kernel(const T* __restrict__ gout,
         store_f32(gx + i, load_f32(out + i) > 0.f ? load_f32(gout + i) : 0.f);
 }
 
-static inline int ew_grid(int64_t nv) {
-    int64_t blocks = (nv + 255) / 256;
-    return (int)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks));
-}
-
 void add_relu_fwd_launch(const void* x, const void* r, void* out, int64_t n,
                          DT dt, hipStream_t s) {
-    if (dt == DT::BF16)
-        hipLaunchKernelGGL((add_relu_fwd_kernel<unsigned short, 8>),
-                           dim3(ew_grid(n / 8)), dim3(256), 0, s,
-                           (const unsigned short*)x, (const unsigned short*)r,
-                           (unsigned short*)out, n);
-    else
-        hipLaunchKernelGGL((add_relu_fwd_kernel<float, 4>),
-                           dim3(ew_grid(n / 4)), dim3(256), 0, s,
-                           (const float*)x, (const float*)r, (float*)out, n);
+    dispatch_dtype(dt, [&](auto t, auto v) {
+        using T = decltype(t);
+        constexpr int V = decltype(v)::value;
+        hipLaunchKernelGGL((add_relu_fwd_kernel<T, V>),
+                           dim3(grid_1d(n / V, 4096)), dim3(256), 0, s,
+                           (const T*)x, (const T*)r, (T*)out, n);
+    });
 }
 
 void add_relu_bwd_launch(const void* gout, const void* out, void* gx, int64_t n,
                          DT dt, hipStream_t s) {
-    if (dt == DT::BF16)
-        hipLaunchKernelGGL((add_relu_bwd_kernel<unsigned short, 8>),
-                           dim3(ew_grid(n / 8)), dim3(256), 0, s,
-                           (const unsigned short*)gout, (const unsigned short*)out,
-                           (unsigned short*)gx, n);
-    else
-        hipLaunchKernelGGL((add_relu_bwd_kernel<float, 4>),
-                           dim3(ew_grid(n / 4)), dim3(256), 0, s,
-                           (const float*)gout, (const float*)out, (float*)gx, n);
+    dispatch_dtype(dt, [&](auto t, auto v) {
+        using T = decltype(t);
+        constexpr int V = decltype(v)::value;
+        hipLaunchKernelGGL((add_relu_bwd_kernel<T, V>),
+                           dim3(grid_1d(n / V, 4096)), dim3(256), 0, s,
+                           (const T*)gout, (const T*)out, (T*)gx, n);
+    });
 }
 
 // --------------------------------------------------------------------------
@@ -248,40 +237,42 @@ __global__ void adam_step_kernel(T* __restrict__ P, const T* __restrict__ G,
 void sgd_step_launch(void* P, const void* G, float* M, float* V, int64_t n,
                      float lr, float mom, float wd, bool nesterov,
                      bool has_master, DT dt, hipStream_t s) {
-    const int grid = ew_grid(n / (dt == DT::BF16 ? 8 : 4));
-    #define FDA_SGD(T, VW, MA, NE)                                              \
-        hipLaunchKernelGGL((sgd_step_kernel<T, VW, MA, NE>), dim3(grid),        \
-                           dim3(256), 0, s, (T*)P, (const T*)G, M, V, n, lr,    \
-                           mom, wd)
-    if (dt == DT::BF16) {
-        if (nesterov) FDA_SGD(unsigned short, 8, true, true);
-        else FDA_SGD(unsigned short, 8, true, false);
-    } else {
-        if (has_master) { if (nesterov) FDA_SGD(float, 4, true, true); else FDA_SGD(float, 4, true, false); }
-        else { if (nesterov) FDA_SGD(float, 4, false, true); else FDA_SGD(float, 4, false, false); }
-    }
-    #undef FDA_SGD
+    dispatch_dtype(dt, [&](auto t, auto v) {
+        using T = decltype(t);
+        constexpr int VW = decltype(v)::value;
+        dispatch_flag(nesterov, [&](auto NE) {
+            auto launch = [&](auto MA) {
+                hipLaunchKernelGGL(
+                    (sgd_step_kernel<T, VW, MA.value, NE.value>),
+                    dim3(grid_1d(n / VW, 4096)), dim3(256), 0, s, (T*)P,
+                    (const T*)G, M, V, n, lr, mom, wd);
+            };
+            // bf16 params always step through their fp32 master
+            if constexpr (sizeof(T) == 2) launch(std::true_type{});
+            else dispatch_flag(has_master, launch);
+        });
+    });
 }
 
 void adam_step_launch(void* P, const void* G, float* M, float* V, float* S,
                       int64_t n, float lr, float b1, float b2, float eps,
                       float wd, float bc1, float bc2, bool has_master, DT dt,
                       hipStream_t s) {
-    const int grid = ew_grid(n / (dt == DT::BF16 ? 8 : 4));
     const float i1 = 1.f / bc1, i2 = 1.f / bc2;
-    #define FDA_ADAM(T, VW, MA)                                                  \
-        hipLaunchKernelGGL((adam_step_kernel<T, VW, MA>), dim3(grid), dim3(256), \
-                           0, s, (T*)P, (const T*)G, M, V, S, n, lr, b1, b2,     \
-                           eps, wd, i1, i2)
-    if (dt == DT::BF16) FDA_ADAM(unsigned short, 8, true);
-    else if (has_master) FDA_ADAM(float, 4, true);
-    else FDA_ADAM(float, 4, false);
-    #undef FDA_ADAM
+    dispatch_dtype(dt, [&](auto t, auto v) {
+        using T = decltype(t);
+        constexpr int VW = decltype(v)::value;
+        auto launch = [&](auto MA) {
+            hipLaunchKernelGGL((adam_step_kernel<T, VW, MA.value>),
+                               dim3(grid_1d(n / VW, 4096)), dim3(256), 0, s,
+                               (T*)P, (const T*)G, M, V, S, n, lr, b1, b2, eps,
+                               wd, i1, i2);
+        };
+        // bf16 params always step through their fp32 master
+        if constexpr (sizeof(T) == 2) launch(std::true_type{});
+        else dispatch_flag(has_master, launch);
+    });
 }
-
-}  // namespace fda
-
-namespace fda {
 
 // G_bf16 += cast(ws_f32): the direct-grad flush for one conv weight slice
 // (replaces an aten cast kernel + an AccumulateGrad add per layer).
@@ -374,8 +365,8 @@ __global__ __launch_bounds__(256) void pad_rows_bf16_kernel(
 void pad_rows_bf16_launch(void* dst, const void* src, long M, int C, int ldl,
                           hipStream_t s) {
     const long nv = M * (long)(ldl / 8);
-    dim3 grid((unsigned)((nv + 255) / 256 < 4096 ? (nv + 255) / 256 : 4096));
-    hipLaunchKernelGGL(pad_rows_bf16_kernel, grid, dim3(256), 0, s,
+    hipLaunchKernelGGL(pad_rows_bf16_kernel, dim3(grid_1d(nv, 4096)),
+                       dim3(256), 0, s,
                        (unsigned short*)dst, (const unsigned short*)src,
                        M, C, ldl);
 }
@@ -403,8 +394,8 @@ __global__ __launch_bounds__(256) void bias_add_rows_bf16_kernel(
 void bias_add_rows_bf16_launch(void* y, const void* bias, long M, int ldl,
                                hipStream_t s) {
     const long nv = M * (long)(ldl / 8);
-    dim3 grid((unsigned)((nv + 255) / 256 < 4096 ? (nv + 255) / 256 : 4096));
-    hipLaunchKernelGGL(bias_add_rows_bf16_kernel, grid, dim3(256), 0, s,
+    hipLaunchKernelGGL(bias_add_rows_bf16_kernel, dim3(grid_1d(nv, 4096)),
+                       dim3(256), 0, s,
                        (unsigned short*)y, (const unsigned short*)bias, M,
                        ldl);
 }

@@ -78,6 +78,14 @@ __device__ __forceinline__ float bn_shift_of(float bias, float mean,
 __device__ __forceinline__ float bn_affine(float x, float scale, float shift) {
     return __fmaf_rn(x, scale, shift);
 }
+// Backward dx of one element: g is the (masked) output gradient, k1/k2 the
+// finalize's sum_g/m and sum_g_xhat/m. Shared by the generic and the fused
+// stem backward-apply kernels, which must agree bit for bit.
+__device__ __forceinline__ float bn_bwd_dx(float g, float xhat, float k1,
+                                           float k2, float weight,
+                                           float invstd) {
+    return (g - k1 - xhat * k2) * weight * invstd;
+}
 // Round V floats through the storage dtype: what a store_f32 + load_f32
 // round trip yields, kept in registers.
 template <typename T, int V>
@@ -156,6 +164,50 @@ __device__ __forceinline__ float block_reduce_max(float v, float* scratch) {
     if (threadIdx.x == 0) scratch[0] = r;
     __syncthreads();
     return scratch[0];
+}
+
+// V per-channel fp32 accumulators of one thread. A struct, so that the fold
+// below can take them by value: an array passed by reference is not split
+// into scalars until the helper has been inlined, and the compiler then
+// keeps it as one <V x float> through the accumulation loop, which costs
+// registers (bn_bwd_stats_kernel<bf16> lost a wave per SIMD that way).
+template <int V> struct ChanAcc { float v[V]; };
+
+// Fold the (s, q) accumulators of a block laid out as (blockDim.x / tpr row
+// groups) x (tpr threads, V channels each) over its row groups, and store
+// the totals as one partial row: out[0][c] = sum s, out[1][c] = sum q, the
+// two halves `stride` floats apart. One array per pass through `smem`
+// (blockDim.x * V floats), groups added in ascending order by the first
+// group's threads — the order every partial row is defined by. Fully
+// unrolled, so s and q stay in registers.
+template <int V>
+__device__ __forceinline__ void block_fold_rows(ChanAcc<V> s, ChanAcc<V> q,
+                                                float* smem, float* out,
+                                                int tpr, int stride) {
+    const int rpb = blockDim.x / tpr;
+    const int lane_c = threadIdx.x % tpr;
+    const int sub_r = threadIdx.x / tpr;
+    #pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+        const float* loc = pass == 0 ? s.v : q.v;
+        #pragma unroll
+        for (int k = 0; k < V; ++k) smem[threadIdx.x * V + k] = loc[k];
+        __syncthreads();
+        if (sub_r == 0) {
+            float acc[V];
+            #pragma unroll
+            for (int k = 0; k < V; ++k) acc[k] = 0.f;
+            for (int rr = 0; rr < rpb; ++rr) {
+                const float* src = smem + (rr * tpr + lane_c) * V;
+                #pragma unroll
+                for (int k = 0; k < V; ++k) acc[k] += src[k];
+            }
+            #pragma unroll
+            for (int k = 0; k < V; ++k)
+                out[pass * stride + lane_c * V + k] = acc[k];
+        }
+        __syncthreads();
+    }
 }
 
 }  // namespace fda

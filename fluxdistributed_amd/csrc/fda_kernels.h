@@ -3,10 +3,33 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <type_traits>
 
 namespace fda {
 
 enum class DT { F32 = 0, BF16 = 1 };
+
+// Host-side dispatch for the launchers: calls f(T{}, V) with the storage
+// type (bf16 bits / float) and its 16 B vector width as an integral
+// constant; dispatch_flag does the same for a bool that selects a template
+// flag. Inside the generic lambda:
+//   using T = decltype(t); constexpr int V = decltype(v)::value;
+template <typename F>
+inline void dispatch_dtype(DT dt, F&& f) {
+    if (dt == DT::BF16) f((unsigned short)0, std::integral_constant<int, 8>{});
+    else f(0.f, std::integral_constant<int, 4>{});
+}
+template <typename F>
+inline void dispatch_flag(bool flag, F&& f) {
+    if (flag) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// 1-D grid for n work items in blocks of 256: at least 1, at most cap
+inline int grid_1d(int64_t n, int cap) {
+    const int64_t b = (n + 255) / 256;
+    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
 
 // fused logit cross-entropy: mean loss over N rows + dlogits in one pass
 void ce_fwd_launch(const void* logits, const int64_t* target, float* loss,
@@ -20,13 +43,12 @@ void add_relu_fwd_launch(const void* x, const void* r, void* out, int64_t n,
 void add_relu_bwd_launch(const void* gout, const void* out, void* gx, int64_t n,
                          DT dt, hipStream_t s);
 
-// BatchNorm(+residual)(+ReLU), NHWC. ws layout (floats):
-//   [0,C)    sum        [C,2C)  sumsq
-//   [2C,3C)  scale      [3C,4C) shift
+// BatchNorm(+residual)(+ReLU), NHWC. ws is 2*C floats:
+//   [0,C)  scale      [C,2C)  shift
 // save_mean/save_invstd are separate C-float buffers.
 int bn_stats_partial_floats(int C, int64_t rows, DT dt);
 // training: stats partials + fused reduce/finalize (running-stat update,
-// scale/shift into ws[2C..4C))
+// scale/shift into ws)
 void bn_stats_launch(const void* x, float* ws, float* part,
                      const float* weight, const float* bias,
                      float* running_mean, float* running_var, float* save_mean,
@@ -35,24 +57,27 @@ void bn_stats_launch(const void* x, float* ws, float* part,
 // pre-fold big conv-epilogue partial sets to NB2 rows at full grid width
 void bn_partial_prefold_launch(const float* part, float* out, int NB,
                                int NB2, int chunkC, hipStream_t s);
-// finalize from conv-epilogue partials ([NB][2][C])
-void bn_finalize_from_partials_launch(
-    const float* part, int NB, const float* weight, const float* bias,
-    float* rm, float* rv, float* save_mean, float* save_invstd, float* ws,
-    int64_t rows, int C, float momentum, float eps, hipStream_t s);
+// fold part[NB][2][chunkC] (channels [c_base, c_base + chunkC) of C) and
+// finalize: what bn_stats_launch runs per chunk, and the whole finalize for
+// conv-epilogue partials (chunkC = C, c_base = 0)
+void bn_fwd_finalize_launch(const float* part, int NB, int chunkC, int c_base,
+                            const float* weight, const float* bias, float* rm,
+                            float* rv, float* save_mean, float* save_invstd,
+                            float* ws, int64_t rows, int C, float momentum,
+                            float eps, hipStream_t s);
 
 // eval: scale/shift from running stats
-void bn_finalize_launch(float* ws, const float* weight, const float* bias,
-                        float* running_mean, float* running_var,
-                        float* save_mean, float* save_invstd, int64_t rows,
-                        int C, bool training, float momentum, float eps,
-                        hipStream_t s);
+void bn_eval_finalize_launch(float* ws, const float* weight,
+                             const float* bias, const float* running_mean,
+                             const float* running_var, float* save_mean,
+                             float* save_invstd, int C, float eps,
+                             hipStream_t s);
 void bn_apply_launch(const void* x, const void* residual, void* out,
                      const float* ws /*scale/shift*/, int64_t rows, int C,
                      bool relu, DT dt, hipStream_t s);
 
-// backward. ws layout (floats): [0,C) sum_g  [C,2C) sum_g_xhat
-//   [2C,3C) k1  [3C,4C) k2   (k's folded with invstd*gamma in finalize)
+// backward. ws is 2*C floats: [0,C) k1 = sum_g/m  [C,2C) k2 = sum_g_xhat/m
+// (both 0 in eval mode).
 // bwd: stats partials + fused reduce/finalize (gw, gb, k1/k2 into ws).
 // With weight+bias (stats) / bias (apply) on a non-residual ReLU BN the
 // ReLU mask is recomputed from x and `out` is never read.
@@ -66,9 +91,14 @@ void bn_bwd_stats_launch(const void* gout, const void* x, const void* out,
 void bn_bwd_apply_launch(const void* gout, const void* x, const void* out,
                          const float* save_mean, const float* save_invstd,
                          const float* weight, const float* ws, void* gx,
-                         void* gres, int64_t rows, int C, bool relu,
-                         bool training, DT dt, hipStream_t s,
-                         const float* bias = nullptr);
+                         void* gres, int64_t rows, int C, bool relu, DT dt,
+                         hipStream_t s, const float* bias = nullptr);
+// fold part[NB][2][chunkC] backward partials: gw/gb (+= when accum), k1/k2
+// into ws. Run per chunk by bn_bwd_stats_launch, and on the fused
+// BN+ReLU+pool backward's partials (chunkC = C, c_base = 0).
+void bn_bwd_finalize_launch(const float* part, int NB, int chunkC, int c_base,
+                            float* ws, float* gw, float* gb, int64_t rows,
+                            int C, bool training, bool accum_g, hipStream_t s);
 
 // MaxPool2d NHWC with saved argmax byte per output element
 void maxpool_fwd_launch(const void* x, void* out, uint8_t* idx, int N, int H,
@@ -80,9 +110,9 @@ void maxpool_bwd_launch(const void* gout, const uint8_t* idx, void* gx, int N,
 
 // Fused stem tail: BN + ReLU + max-pool (pool.hip). Needs 256 % (C/V) == 0
 // (V = 8 bf16 / 4 fp32), KH*KW <= 255 and ceil(K/S) <= 2. fwd consumes the scale/shift the
-// forward finalize left in ws[2C..4C) and writes only the pooled tensor and
-// its argmax bytes. bwd stats writes [bn_relu_maxpool_bwd_blocks][2][C]
-// partials for bn_bwd_reduce_finalize; bwd apply reads k1/k2 from ws.
+// forward finalize left in ws and writes only the pooled tensor and its
+// argmax bytes. bwd stats writes [bn_relu_maxpool_bwd_blocks][2][C]
+// partials for bn_bwd_finalize_launch; bwd apply reads k1/k2 from ws.
 void bn_relu_maxpool_fwd_launch(const void* x, const float* ws, void* out,
                                 uint8_t* idx, int N, int H, int W, int C,
                                 int HO, int WO, int KH, int KW, int S, int P,
@@ -98,11 +128,6 @@ void bn_relu_maxpool_bwd_apply_launch(
     const float* save_mean, const float* save_invstd, const float* weight,
     const float* bias, const float* ws, void* gx, int N, int H, int W, int C,
     int HO, int WO, int KH, int KW, int S, int P, DT dt, hipStream_t s);
-// fold [NB][2][C] backward partials: gw/gb (+= when accum), k1/k2 into ws
-void bn_bwd_finalize_from_partials_launch(const float* part, int NB,
-                                          float* ws, float* gw, float* gb,
-                                          int64_t rows, int C, bool training,
-                                          bool accum_g, hipStream_t s);
 
 // global average pool (NHWC): y[n][c] = mean_hw x; gx = gy/HW broadcast
 void gap_fwd_launch(const void* x, void* y, int N, int HW, int C, DT dt,

@@ -127,41 +127,30 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(
     }
 }
 
-static inline int pool_grid(int64_t total) {
-    int64_t b = (total + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
-
 void maxpool_fwd_launch(const void* x, void* out, uint8_t* idx, int N, int H,
                         int W, int C, int HO, int WO, int KH, int KW, int S,
                         int P, DT dt, hipStream_t s) {
-    if (dt == DT::BF16)
-        hipLaunchKernelGGL((maxpool_fwd_kernel<unsigned short, 8>),
-                           dim3(pool_grid((int64_t)N * HO * WO * C / 8)),
-                           dim3(256), 0, s, (const unsigned short*)x,
-                           (unsigned short*)out, idx, N, H, W, C, HO, WO, KH,
-                           KW, S, P);
-    else
-        hipLaunchKernelGGL((maxpool_fwd_kernel<float, 4>),
-                           dim3(pool_grid((int64_t)N * HO * WO * C / 4)),
-                           dim3(256), 0, s, (const float*)x, (float*)out, idx,
-                           N, H, W, C, HO, WO, KH, KW, S, P);
+    dispatch_dtype(dt, [&](auto t, auto v) {
+        using T = decltype(t);
+        constexpr int V = decltype(v)::value;
+        hipLaunchKernelGGL((maxpool_fwd_kernel<T, V>),
+                           dim3(grid_1d((int64_t)N * HO * WO * C / V, 4096)),
+                           dim3(256), 0, s, (const T*)x, (T*)out, idx, N, H, W,
+                           C, HO, WO, KH, KW, S, P);
+    });
 }
 
 void maxpool_bwd_launch(const void* gout, const uint8_t* idx, void* gx, int N,
                         int H, int W, int C, int HO, int WO, int KH, int KW,
                         int S, int P, DT dt, hipStream_t s) {
     const unsigned rows = (unsigned)((int64_t)N * H);
-    if (dt == DT::BF16)
-        hipLaunchKernelGGL((maxpool_bwd_kernel<unsigned short, 8>),
-                           dim3(rows), dim3(256), 0, s,
-                           (const unsigned short*)gout, idx,
-                           (unsigned short*)gx, N, H, W, C, HO, WO, KH, KW, S,
-                           P);
-    else
-        hipLaunchKernelGGL((maxpool_bwd_kernel<float, 4>),
-                           dim3(rows), dim3(256), 0, s, (const float*)gout,
-                           idx, (float*)gx, N, H, W, C, HO, WO, KH, KW, S, P);
+    dispatch_dtype(dt, [&](auto t, auto v) {
+        using T = decltype(t);
+        constexpr int V = decltype(v)::value;
+        hipLaunchKernelGGL((maxpool_bwd_kernel<T, V>), dim3(rows), dim3(256),
+                           0, s, (const T*)gout, idx, (T*)gx, N, H, W, C, HO,
+                           WO, KH, KW, S, P);
+    });
 }
 
 // ---- fused stem tail: BN + ReLU + max-pool --------------------------------
@@ -370,14 +359,15 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_stats_kernel(
     const int sub_r = threadIdx.x / CV;
     const int c0 = lane_c * V;
 
-    float mu[V], is[V], sc[V], sh[V], sg[V], sgx[V];
+    float mu[V], is[V], sc[V], sh[V];
+    ChanAcc<V> sg, sgx;
     #pragma unroll
     for (int k = 0; k < V; ++k) {
         mu[k] = mean[c0 + k];
         is[k] = invstd[c0 + k];
         sc[k] = bn_scale_of(weight[c0 + k], is[k]);
         sh[k] = bn_shift_of(bias[c0 + k], mu[k], sc[k]);
-        sg[k] = sgx[k] = 0.f;
+        sg.v[k] = sgx.v[k] = 0.f;
     }
     const int NR = N * H;
     const int r_begin = blockIdx.x * rows_per_block;
@@ -401,33 +391,13 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_stats_kernel(
                 const float gm =
                     bn_relu_positive<T>(xf, sc[k], sh[k]) ? g[k] : 0.f;
                 const float xhat = (xf - mu[k]) * is[k];
-                sg[k] += gm;
-                sgx[k] += gm * xhat;
+                sg.v[k] += gm;
+                sgx.v[k] += gm * xhat;
             }
         }
     }
-    float* outp = part + (int64_t)blockIdx.x * 2 * C;
-    #pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        float* loc = pass == 0 ? sg : sgx;
-        #pragma unroll
-        for (int k = 0; k < V; ++k) smem[threadIdx.x * V + k] = loc[k];
-        __syncthreads();
-        if (sub_r == 0) {
-            float acc[V];
-            #pragma unroll
-            for (int k = 0; k < V; ++k) acc[k] = 0.f;
-            for (int rr = 0; rr < rpb; ++rr) {
-                const float* src = smem + (rr * CV + lane_c) * V;
-                #pragma unroll
-                for (int k = 0; k < V; ++k) acc[k] += src[k];
-            }
-            #pragma unroll
-            for (int k = 0; k < V; ++k)
-                outp[pass * C + lane_c * V + k] = acc[k];
-        }
-        __syncthreads();
-    }
+    block_fold_rows<V>(sg, sgx, smem, part + (int64_t)blockIdx.x * 2 * C, CV,
+                       C);
 }
 
 // bwd apply: one block per (n, hi) input row; writes gx for the stem wgrad.
@@ -477,9 +447,8 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_apply_kernel(
             const float gm =
                 bn_relu_positive<T>(xf, sc[k], sh[k]) ? g[k] : 0.f;
             const float xhat = (xf - mu[k]) * is[k];
-            // bn_bwd_apply_kernel's expression
-            const float r = (gm - a1[k] - xhat * a2[k]) * wk[k] * is[k];
-            store_f32(rv + k, r);
+            store_f32(rv + k,
+                      bn_bwd_dx(gm, xhat, a1[k], a2[k], wk[k], is[k]));
         }
         *(uint4*)(gxrow + (int64_t)wi * C + c0) = *(uint4*)rv;
     }
@@ -489,25 +458,23 @@ void bn_relu_maxpool_fwd_launch(const void* x, const float* ws, void* out,
                                 uint8_t* idx, int N, int H, int W, int C,
                                 int HO, int WO, int KH, int KW, int S, int P,
                                 DT dt, hipStream_t s) {
-    const float* scale = ws + 2 * C;
-    const float* shift = ws + 3 * C;
+    const float* scale = ws;
+    const float* shift = ws + C;
     const unsigned rows = (unsigned)((int64_t)N * HO);
-    #define FDA_BNPOOL(T, VW, KS_)                                              \
-        hipLaunchKernelGGL((bn_relu_maxpool_fwd_kernel<T, VW, KS_>),            \
-                           dim3(rows), dim3(256), 0, s, (const T*)x, scale,     \
-                           shift, (T*)out, idx, N, H, W, C, HO, WO, KH, KW, S,  \
-                           P)
     const int ks = KH == KW && (KH == 3 || KH == 2) ? KH : 0;
-    if (dt == DT::BF16) {
-        if (ks == 3) FDA_BNPOOL(unsigned short, 8, 3);
-        else if (ks == 2) FDA_BNPOOL(unsigned short, 8, 2);
-        else FDA_BNPOOL(unsigned short, 8, 0);
-    } else {
-        if (ks == 3) FDA_BNPOOL(float, 4, 3);
-        else if (ks == 2) FDA_BNPOOL(float, 4, 2);
-        else FDA_BNPOOL(float, 4, 0);
-    }
-    #undef FDA_BNPOOL
+    dispatch_dtype(dt, [&](auto t, auto v) {
+        using T = decltype(t);
+        constexpr int V = decltype(v)::value;
+        auto launch = [&](auto KS) {
+            hipLaunchKernelGGL((bn_relu_maxpool_fwd_kernel<T, V, KS.value>),
+                               dim3(rows), dim3(256), 0, s, (const T*)x, scale,
+                               shift, (T*)out, idx, N, H, W, C, HO, WO, KH, KW,
+                               S, P);
+        };
+        if (ks == 3) launch(std::integral_constant<int, 3>{});
+        else if (ks == 2) launch(std::integral_constant<int, 2>{});
+        else launch(std::integral_constant<int, 0>{});
+    });
 }
 
 // Grid of the fused bwd stats pass == rows of its partial buffer. Capped at
@@ -537,20 +504,15 @@ void bn_relu_maxpool_bwd_stats_launch(
     int WO, int KH, int KW, int S, int P, DT dt, hipStream_t s) {
     int grid, rpb;
     pool_stats_geom((int64_t)N * H, grid, rpb);
-    const int V = dt == DT::BF16 ? 8 : 4;
-    const int shmem = 256 * V * (int)sizeof(float);
-    if (dt == DT::BF16)
-        hipLaunchKernelGGL(
-            (bn_relu_maxpool_bwd_stats_kernel<unsigned short, 8>), dim3(grid),
-            dim3(256), shmem, s, (const unsigned short*)gout, idx,
-            (const unsigned short*)x, save_mean, save_invstd, weight, bias,
-            part, N, H, W, C, HO, WO, KH, KW, S, P, rpb);
-    else
-        hipLaunchKernelGGL((bn_relu_maxpool_bwd_stats_kernel<float, 4>),
-                           dim3(grid), dim3(256), shmem, s,
-                           (const float*)gout, idx, (const float*)x,
-                           save_mean, save_invstd, weight, bias, part, N, H,
-                           W, C, HO, WO, KH, KW, S, P, rpb);
+    dispatch_dtype(dt, [&](auto t, auto v) {
+        using T = decltype(t);
+        constexpr int V = decltype(v)::value;
+        hipLaunchKernelGGL((bn_relu_maxpool_bwd_stats_kernel<T, V>),
+                           dim3(grid), dim3(256), 256 * V * sizeof(float), s,
+                           (const T*)gout, idx, (const T*)x, save_mean,
+                           save_invstd, weight, bias, part, N, H, W, C, HO, WO,
+                           KH, KW, S, P, rpb);
+    });
 }
 
 void bn_relu_maxpool_bwd_apply_launch(
@@ -558,26 +520,18 @@ void bn_relu_maxpool_bwd_apply_launch(
     const float* save_mean, const float* save_invstd, const float* weight,
     const float* bias, const float* ws, void* gx, int N, int H, int W, int C,
     int HO, int WO, int KH, int KW, int S, int P, DT dt, hipStream_t s) {
-    const float* k1 = ws + 2 * C;
-    const float* k2 = ws + 3 * C;
+    const float* k1 = ws;
+    const float* k2 = ws + C;
     const unsigned rows = (unsigned)((int64_t)N * H);
-    if (dt == DT::BF16)
-        hipLaunchKernelGGL(
-            (bn_relu_maxpool_bwd_apply_kernel<unsigned short, 8>), dim3(rows),
-            dim3(256), 0, s, (const unsigned short*)gout, idx,
-            (const unsigned short*)x, save_mean, save_invstd, weight, bias,
-            k1, k2, (unsigned short*)gx, N, H, W, C, HO, WO, KH, KW, S, P);
-    else
-        hipLaunchKernelGGL((bn_relu_maxpool_bwd_apply_kernel<float, 4>),
-                           dim3(rows), dim3(256), 0, s, (const float*)gout,
-                           idx, (const float*)x, save_mean, save_invstd,
-                           weight, bias, k1, k2, (float*)gx, N, H, W, C, HO,
-                           WO, KH, KW, S, P);
+    dispatch_dtype(dt, [&](auto t, auto v) {
+        using T = decltype(t);
+        constexpr int V = decltype(v)::value;
+        hipLaunchKernelGGL((bn_relu_maxpool_bwd_apply_kernel<T, V>),
+                           dim3(rows), dim3(256), 0, s, (const T*)gout, idx,
+                           (const T*)x, save_mean, save_invstd, weight, bias,
+                           k1, k2, (T*)gx, N, H, W, C, HO, WO, KH, KW, S, P);
+    });
 }
-
-}  // namespace fda
-
-namespace fda {
 
 // ---- global average pool (AdaptiveMeanPool 1x1), NHWC -------------------
 // "AdaptiveMeanPool / global avg pool fwd/bwd — warp
@@ -630,30 +584,24 @@ __global__ __launch_bounds__(256) void gap_bwd_kernel(
 
 void gap_fwd_launch(const void* x, void* y, int N, int HW, int C, DT dt,
                     hipStream_t s) {
-    const int V = dt == DT::BF16 ? 8 : 4;
-    const long nv = (long)N * (C / V);
-    dim3 grid((unsigned)((nv + 255) / 256 < 1024 ? (nv + 255) / 256 : 1024));
-    if (dt == DT::BF16)
-        hipLaunchKernelGGL((gap_fwd_kernel<unsigned short, 8>), grid,
-                           dim3(256), 0, s, (const unsigned short*)x,
-                           (unsigned short*)y, N, HW, C);
-    else
-        hipLaunchKernelGGL((gap_fwd_kernel<float, 4>), grid, dim3(256), 0, s,
-                           (const float*)x, (float*)y, N, HW, C);
+    dispatch_dtype(dt, [&](auto t, auto v) {
+        using T = decltype(t);
+        constexpr int V = decltype(v)::value;
+        hipLaunchKernelGGL((gap_fwd_kernel<T, V>),
+                           dim3(grid_1d((int64_t)N * (C / V), 1024)),
+                           dim3(256), 0, s, (const T*)x, (T*)y, N, HW, C);
+    });
 }
 
 void gap_bwd_launch(const void* gy, void* gx, int N, int HW, int C, DT dt,
                     hipStream_t s) {
-    const int V = dt == DT::BF16 ? 8 : 4;
-    const long nv = (long)N * HW * (C / V);
-    dim3 grid((unsigned)((nv + 255) / 256 < 4096 ? (nv + 255) / 256 : 4096));
-    if (dt == DT::BF16)
-        hipLaunchKernelGGL((gap_bwd_kernel<unsigned short, 8>), grid,
-                           dim3(256), 0, s, (const unsigned short*)gy,
-                           (unsigned short*)gx, N, HW, C);
-    else
-        hipLaunchKernelGGL((gap_bwd_kernel<float, 4>), grid, dim3(256), 0, s,
-                           (const float*)gy, (float*)gx, N, HW, C);
+    dispatch_dtype(dt, [&](auto t, auto v) {
+        using T = decltype(t);
+        constexpr int V = decltype(v)::value;
+        hipLaunchKernelGGL((gap_bwd_kernel<T, V>),
+                           dim3(grid_1d((int64_t)N * HW * (C / V), 4096)),
+                           dim3(256), 0, s, (const T*)gy, (T*)gx, N, HW, C);
+    });
 }
 
 }  // namespace fda

@@ -8,7 +8,6 @@ Numerics contract (tests/test_ops_gpu.py): every native kernel is compared
 against the plain fp32 PyTorch composition of the same op.
 """
 
-import os
 from typing import Optional
 
 import torch
@@ -139,6 +138,32 @@ class MaxPool2d(torch.nn.Module):
 # --------------------------------------------------------------------------
 
 
+def _direct_grad_slices(weight, bias):
+    """Direct grads: when both BN params live in a fused-optimizer flat
+    buffer, the backward finalize kernel += 's into their G slices and no
+    AccumulateGrad kernels run (ops/fused_optim.FLAT_SLICES). Returns the
+    (gw, gb) slices, or (None, None)."""
+    from .fused_optim import flat_grad_slice
+
+    gw_sl = flat_grad_slice(weight)
+    gb_sl = flat_grad_slice(bias)
+    if gw_sl is None or gb_sl is None:
+        return None, None
+    return gw_sl, gb_sl
+
+
+def _param_grads(weight, bias, gw, gb, direct: bool):
+    """What backward returns for (weight, bias): the kernel's gw/gb, or
+    None after telling the bucketer that the flat G slices were written."""
+    if not direct:
+        return gw, gb
+    from ..parallel.bucketing import notify_grad_written
+
+    notify_grad_written(weight)
+    notify_grad_written(bias)
+    return None, None
+
+
 class _BNAct(torch.autograd.Function):
     @staticmethod
     def forward(
@@ -185,30 +210,17 @@ class _BNAct(torch.autograd.Function):
         x, weight, save_mean, save_invstd, out = ctx.saved_tensors
         bias = ctx.bn_bias
         C = require_native("batch_norm_act")
-        # direct grads: when the params live in a fused-optimizer flat
-        # buffer, the finalize kernel += 's into the G slices and no
-        # AccumulateGrad kernels run (ops/fused_optim.FLAT_SLICES).
-        from .fused_optim import flat_grad_slice
-
-        gw_sl = flat_grad_slice(weight)
-        gb_sl = flat_grad_slice(bias) if bias is not None else None
-        direct = gw_sl is not None and gb_sl is not None
+        gw_sl, gb_sl = _direct_grad_slices(weight, bias)
         want_gres = ctx.has_residual and ctx.relu
         # bias lets a non-residual ReLU BN recompute its mask from x (which
-        # both kernels load anyway) instead of reading `out` twice
-        mask_bias = bias if _mask_from_x() else None
+        # both kernels load anyway) instead of reading `out` twice; the
+        # binding ignores it for residual and non-ReLU BNs
         gx, gw, gb, gres_k = C.bn_act_bwd(
             grad_out.contiguous(memory_format=torch.channels_last),
             x, weight, save_mean, save_invstd, out, ctx.relu, ctx.training,
-            gw_sl if direct else None, gb_sl if direct else None, want_gres,
-            mask_bias,
+            gw_sl, gb_sl, want_gres, bias,
         )
-        if direct:
-            from ..parallel.bucketing import notify_grad_written
-
-            notify_grad_written(weight)
-            notify_grad_written(bias)
-            gw = gb = None
+        gw, gb = _param_grads(weight, bias, gw, gb, gw_sl is not None)
         gres = None
         if ctx.has_residual:
             # d(out)/d(residual) = relu-mask * grad_out: a byproduct of the
@@ -220,12 +232,6 @@ class _BNAct(torch.autograd.Function):
             stash_junction_gres(ctx.res_key, gres)
             gres = None     # the conv dgrad epilogue folds it into dx
         return gx, gw, gb, None, None, None, None, None, None, gres, None
-
-
-def _mask_from_x() -> bool:
-    """FLUXDIST_BN_XMASK=0 keeps the backward ReLU mask on the saved output
-    (A/B knob, docs/kernels.md)."""
-    return os.environ.get("FLUXDIST_BN_XMASK", "1") != "0"
 
 
 class _BNActPool(torch.autograd.Function):
@@ -256,25 +262,13 @@ class _BNActPool(torch.autograd.Function):
         x, weight, bias, save_mean, save_invstd, idx = ctx.saved_tensors
         k, s, p = ctx.geom
         C = require_native("batch_norm_act_pool")
-        # direct grads into the fused optimizer's flat G slices, as in
-        # _BNAct.backward
-        from .fused_optim import flat_grad_slice
-
-        gw_sl = flat_grad_slice(weight)
-        gb_sl = flat_grad_slice(bias)
-        direct = gw_sl is not None and gb_sl is not None
+        gw_sl, gb_sl = _direct_grad_slices(weight, bias)
         gx, gw, gb = C.bn_act_pool_bwd(
             grad_out.contiguous(memory_format=torch.channels_last),
             x, weight, bias, save_mean, save_invstd, idx, k, k, s, p,
-            ctx.training,
-            gw_sl if direct else None, gb_sl if direct else None,
+            ctx.training, gw_sl, gb_sl,
         )
-        if direct:
-            from ..parallel.bucketing import notify_grad_written
-
-            notify_grad_written(weight)
-            notify_grad_written(bias)
-            gw = gb = None
+        gw, gb = _param_grads(weight, bias, gw, gb, gw_sl is not None)
         return gx, gw, gb, None, None, None, None, None, None, None, None
 
 

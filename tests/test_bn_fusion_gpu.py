@@ -1,5 +1,5 @@
 """conv->BN stats-fusion numerics: the conv epilogue's per-tile sum/sumsq
-partials (bn_finalize_from_partials) must give the same batch stats,
+partials (bn_fwd_finalize_launch) must give the same batch stats,
 output, running stats and gradients as BN's own stats pass. This path was
 dead until r2 (grad mode is invisible inside Function.forward) — this is
 its dedicated hardware oracle."""
