@@ -52,6 +52,11 @@ def main():
         from fluxdistributed_amd.utils.precision import to_mixed_bf16
 
         model = to_mixed_bf16(model.to(memory_format=torch.channels_last))
+    # forward-only execution: conv + BN (+ residual + ReLU) as one kernel on
+    # the GPU, the model's own ops elsewhere
+    from fluxdistributed_amd import compile_for_inference
+
+    infer = compile_for_inference(model)
 
     names = None
     if args.labels:
@@ -62,8 +67,7 @@ def main():
     x = torch.stack([load_image(pth) for pth in args.images]).to(device)
     if device.type == "cuda":
         x = x.bfloat16().contiguous(memory_format=torch.channels_last)
-    with torch.no_grad():
-        logits = model(x).float().cpu()
+    logits = infer(x).float().cpu()
     probs = torch.softmax(logits, dim=-1)
     top = torch.topk(probs, min(args.topk, probs.shape[-1]), dim=-1)
     for i, pth in enumerate(args.images):

@@ -21,7 +21,7 @@ from fluxdistributed_amd.utils.checkpoint import load_checkpoint
 from fluxdistributed_amd.data.preprocess import preprocess
 
 
-def build_app(model, device, names=None, topk=3):
+def build_app(model, device, names=None, topk=3, bf16=False):
     from fastapi import FastAPI, Request
 
     app = FastAPI(title="fluxdistributed_amd classifier")
@@ -37,6 +37,9 @@ def build_app(model, device, names=None, topk=3):
         with Image.open(io.BytesIO(data)) as im:
             arr = np.asarray(im.convert("RGB"), dtype="float32") / 255.0
         x = preprocess(torch.from_numpy(arr).permute(2, 0, 1)).unsqueeze(0).to(device)
+        if bf16:
+            # the native kernel path takes channels_last bf16
+            x = x.bfloat16().contiguous(memory_format=torch.channels_last)
         with torch.no_grad():
             probs = torch.softmax(model(x).float().cpu()[0], dim=-1)
         top = torch.topk(probs, min(topk, probs.shape[-1]))
@@ -69,6 +72,15 @@ def main():
     model.eval()
     device = torch.device("cuda:0") if torch.cuda.is_available() else torch.device("cpu")
     model = model.to(device)
+    if device.type == "cuda":
+        from fluxdistributed_amd.utils.precision import to_mixed_bf16
+
+        model = to_mixed_bf16(model.to(memory_format=torch.channels_last))
+    # forward-only execution with the BN coefficients snapshotted once: the
+    # weights of a server do not change under it
+    from fluxdistributed_amd import compile_for_inference
+
+    model = compile_for_inference(model).freeze()
     names = None
     if args.labels:
         from fluxdistributed_amd.data.imagenet import labels
@@ -77,7 +89,8 @@ def main():
 
     import uvicorn
 
-    uvicorn.run(build_app(model, device, names), host=args.host, port=args.port)
+    uvicorn.run(build_app(model, device, names, bf16=device.type == "cuda"),
+                host=args.host, port=args.port)
 
 
 if __name__ == "__main__":

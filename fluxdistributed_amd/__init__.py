@@ -38,4 +38,6 @@ from .data.imagenet import minibatch, minibatch_raw, train_solutions, labels  # 
 from .data.preprocess import RawBatch, pack_images, preprocess_batch  # noqa: F401
 from .utils.metrics import topkaccuracy  # noqa: F401
 
+from .inference import InferenceModel, compile_for_inference  # noqa: F401
+
 from . import models, ops, parallel, data, utils  # noqa: F401

@@ -736,6 +736,163 @@ std::tuple<at::Tensor, at::Tensor> conv_stem_fwd_stats(
     return conv_stem_fwd_impl(x8, wpad, R, sy, sx, P, Q, true);
 }
 
+// The config a forward conv of this geometry runs: (BM, BN, SK, ring), from
+// the functions the launcher itself obeys. For tests that must know which
+// kernel a shape reaches.
+std::tuple<int64_t, int64_t, int64_t, bool> conv_igemm_fwd_config(
+    int64_t M, int64_t C, int64_t K, int64_t R, int64_t S) {
+    TORCH_CHECK(M >= 1 && C >= 64 && C % 64 == 0 && K >= 64 && K % 64 == 0 &&
+                    R >= 1 && S >= 1,
+                "conv_igemm_fwd_config: bad geometry");
+    int BM, BN, SK;
+    fda::conv_igemm_plan((long)M, (int)K, (long)R * S * (C / 64), 1, &BM, &BN,
+                         &SK);
+    const long blocks = ((M + BM - 1) / BM) * (K / BN) * SK;
+    return {BM, BN, SK, fda::conv_igemm_ring(blocks, BN)};
+}
+
+// ---- inference forward: conv + eval BN + residual + ReLU in one kernel ----
+// Shape, dtype and layout checks come first and check_device last, so every
+// refusal can be exercised on a machine without a GPU.
+
+// scale/shift of the inference epilogue: K floats each
+static void check_epilogue_coeffs(const char* op, const at::Tensor& scale,
+                                  const at::Tensor& shift, int64_t K) {
+    check_flat(op, "scale", scale, at::kFloat, K);
+    check_flat(op, "shift", shift, at::kFloat, K);
+    // the kernels read them as 16-B vectors
+    TORCH_CHECK((reinterpret_cast<uintptr_t>(scale.data_ptr()) & 15) == 0 &&
+                    (reinterpret_cast<uintptr_t>(shift.data_ptr()) & 15) == 0,
+                op, ": scale and shift must be 16-byte aligned");
+}
+
+// y = bf16(relu(scale[k] * conv(x, w) + shift[k] + residual)), rounded once
+// from the fp32 accumulator. residual: an empty tensor for none, else bf16
+// channels_last of exactly the output's shape. The output is allocated
+// here, so no operand can alias it.
+at::Tensor conv_igemm_fwd_fused(at::Tensor x, at::Tensor w, at::Tensor scale,
+                                at::Tensor shift, at::Tensor residual,
+                                bool relu, int64_t sy, int64_t sx, int64_t py,
+                                int64_t px) {
+    const char* op = "conv_igemm_fwd_fused";
+    TORCH_CHECK(x.dim() == 4 && w.dim() == 4 &&
+                    x.scalar_type() == at::kBFloat16 &&
+                    w.scalar_type() == at::kBFloat16 &&
+                    x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                    w.is_contiguous(at::MemoryFormat::ChannelsLast),
+                op, ": x and w must be 4-D channels_last bf16");
+    const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2),
+              W = (int)x.size(3);
+    const int K = (int)w.size(0), R = (int)w.size(2), S = (int)w.size(3);
+    TORCH_CHECK(C % 64 == 0 && K % 64 == 0 && C >= 64 && K >= 64, op,
+                ": C and K must be multiples of 64");
+    TORCH_CHECK((int)w.size(1) == C, op, ": channel mismatch");
+    TORCH_CHECK(N >= 1 && sy >= 1 && sx >= 1 && py >= 0 && px >= 0 &&
+                    H + 2 * py >= R && W + 2 * px >= S,
+                op, ": bad stride/padding or filter larger than the input");
+    const int P = (H + 2 * (int)py - R) / (int)sy + 1;
+    const int Q = (W + 2 * (int)px - S) / (int)sx + 1;
+    check_epilogue_coeffs(op, scale, shift, K);
+    const bool has_res = residual.defined() && residual.numel() > 0;
+    if (has_res)
+        TORCH_CHECK(residual.scalar_type() == at::kBFloat16 &&
+                        residual.dim() == 4 && residual.size(0) == N &&
+                        residual.size(1) == K && residual.size(2) == P &&
+                        residual.size(3) == Q &&
+                        residual.is_contiguous(at::MemoryFormat::ChannelsLast),
+                    op, ": residual must be channels_last bf16 of the "
+                    "output's shape [", N, ",", K, ",", P, ",", Q, "]");
+    if (has_res)
+        TORCH_CHECK((reinterpret_cast<uintptr_t>(residual.data_ptr()) & 15) == 0,
+                    op, ": residual must be 16-byte aligned");
+    const long M = (long)N * P * Q;
+    int BM, BN, SK;
+    fda::conv_igemm_plan(M, K, (long)R * S * (C / 64), 1, &BM, &BN, &SK);
+    if (SK > 1)
+        TORCH_CHECK(K <= 2048, op, ": split-K shapes need K <= 2048");
+    check_device(op, {x, w, scale, shift, has_res ? residual : at::Tensor()});
+    auto y = at::empty({N, K, P, Q},
+                       x.options().memory_format(at::MemoryFormat::ChannelsLast));
+    const void* resp = has_res ? residual.data_ptr() : nullptr;
+    if (SK > 1) {
+        // fp32 partials from the plain forward; the combine kernel applies
+        // the epilogue, so these shapes stay fused as well
+        auto skp = at::empty({(long)SK * M * K}, x.options().dtype(at::kFloat));
+        fda::conv_igemm_launch(x.data_ptr(), w.data_ptr(), y.data_ptr(), N, H,
+                               W, C, K, P, Q, R, S, (int)sy, (int)sx, (int)py,
+                               (int)px, /*dgrad=*/false, cur_stream(), nullptr,
+                               skp.data_ptr<float>(), SK);
+        fda::conv_skcombine_fused_launch(
+            skp.data_ptr<float>(), y.data_ptr(), M, K, SK,
+            fda::conv_skcombine_blocks(M, K), scale.data_ptr<float>(),
+            shift.data_ptr<float>(), resp, relu, cur_stream());
+        return y;
+    }
+    fda::conv_igemm_fwd_fused_launch(
+        x.data_ptr(), w.data_ptr(), y.data_ptr(), N, H, W, C, K, P, Q, R, S,
+        (int)sy, (int)sx, (int)py, (int)px, scale.data_ptr<float>(),
+        shift.data_ptr<float>(), resp, relu, cur_stream());
+    return y;
+}
+
+// stem conv + eval BN (+ ReLU); operands as conv_stem_fwd
+at::Tensor conv_stem_fwd_fused(at::Tensor x8, at::Tensor wpad,
+                               at::Tensor scale, at::Tensor shift, bool relu,
+                               int64_t R, int64_t sy, int64_t sx, int64_t P,
+                               int64_t Q) {
+    const char* op = "conv_stem_fwd_fused";
+    TORCH_CHECK(wpad.dim() == 3 && wpad.is_contiguous() &&
+                    wpad.scalar_type() == at::kBFloat16 &&
+                    wpad.size(1) == R && wpad.size(2) == 64,
+                op, ": wpad must be contiguous bf16 [K][R][64]");
+    const int K = (int)wpad.size(0);
+    check_stem_geometry(op, x8, K, R, sy, sx, P, Q);
+    check_epilogue_coeffs(op, scale, shift, K);
+    check_device(op, {x8, wpad, scale, shift});
+    const int N = (int)x8.size(0), Hp = (int)x8.size(2), Wp = (int)x8.size(3);
+    auto y = at::empty({N, K, P, Q},
+                       x8.options().memory_format(at::MemoryFormat::ChannelsLast));
+    fda::conv_stem_fwd_fused_launch(
+        x8.data_ptr(), wpad.data_ptr(), y.data_ptr(), N, Hp, Wp, K, (int)P,
+        (int)Q, (int)R, (int)sy, (int)sx, scale.data_ptr<float>(),
+        shift.data_ptr<float>(), relu, cur_stream());
+    return y;
+}
+
+// One launch folds the eval-mode BN of every layer into the fp32 arena:
+// layer t writes scale[Cs[t]] then shift[Cs[t]] at arena + offs[t]. The
+// tables are device tensors of equal length: int64 addresses of the fp32
+// weight / bias / running_mean / running_var, int32 channel counts, int64
+// arena offsets (in floats) and fp32 eps. The kernel skips a layer whose
+// slice would leave the arena.
+void bn_fold_eval_batch(at::Tensor w_ptrs, at::Tensor b_ptrs,
+                        at::Tensor rm_ptrs, at::Tensor rv_ptrs, at::Tensor Cs,
+                        at::Tensor offs, at::Tensor eps, at::Tensor arena,
+                        int64_t max_c) {
+    const char* op = "bn_fold_eval_batch";
+    const int64_t n = w_ptrs.numel();
+    TORCH_CHECK(n >= 1 && n <= 65535, op, ": need 1..65535 layers, got ", n);
+    check_flat(op, "w_ptrs", w_ptrs, at::kLong, n);
+    check_flat(op, "b_ptrs", b_ptrs, at::kLong, n);
+    check_flat(op, "rm_ptrs", rm_ptrs, at::kLong, n);
+    check_flat(op, "rv_ptrs", rv_ptrs, at::kLong, n);
+    check_flat(op, "Cs", Cs, at::kInt, n);
+    check_flat(op, "offs", offs, at::kLong, n);
+    check_flat(op, "eps", eps, at::kFloat, n);
+    TORCH_CHECK(arena.scalar_type() == at::kFloat && arena.dim() == 1 &&
+                    arena.is_contiguous(),
+                op, ": arena must be 1-D contiguous fp32");
+    TORCH_CHECK(max_c >= 1 && 2 * max_c <= arena.numel(), op,
+                ": max_c must be in [1, arena/2], got ", max_c);
+    check_device(op, {w_ptrs, b_ptrs, rm_ptrs, rv_ptrs, Cs, offs, eps, arena});
+    fda::bn_fold_eval_batch_launch(
+        w_ptrs.data_ptr<int64_t>(), b_ptrs.data_ptr<int64_t>(),
+        rm_ptrs.data_ptr<int64_t>(), rv_ptrs.data_ptr<int64_t>(),
+        Cs.data_ptr<int>(), offs.data_ptr<int64_t>(), eps.data_ptr<float>(),
+        arena.data_ptr<float>(), arena.numel(), (int)n, (int)max_c,
+        cur_stream());
+}
+
 at::Tensor conv_stem_wgrad(at::Tensor dy, at::Tensor x8, int64_t R,
                            int64_t sy, int64_t sx) {
     const char* op = "conv_stem_wgrad";
@@ -983,6 +1140,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("colsum_accum_bf16", &colsum_accum_bf16);
     m.def("conv_stem_fwd", &conv_stem_fwd);
     m.def("conv_stem_wgrad", &conv_stem_wgrad);
+    m.def("conv_igemm_fwd_config", &conv_igemm_fwd_config,
+          pybind11::arg("M"), pybind11::arg("C"), pybind11::arg("K"),
+          pybind11::arg("R"), pybind11::arg("S"),
+          "(BM, BN, SK, ring) of a forward conv with M output pixels");
+    m.def("conv_igemm_fwd_fused", &conv_igemm_fwd_fused, pybind11::arg("x"),
+          pybind11::arg("w"), pybind11::arg("scale"), pybind11::arg("shift"),
+          pybind11::arg("residual"), pybind11::arg("relu"),
+          pybind11::arg("sy"), pybind11::arg("sx"), pybind11::arg("py"),
+          pybind11::arg("px"),
+          "conv + eval BN + residual + ReLU, one bf16 round (inference)");
+    m.def("conv_stem_fwd_fused", &conv_stem_fwd_fused, pybind11::arg("x8"),
+          pybind11::arg("wpad"), pybind11::arg("scale"),
+          pybind11::arg("shift"), pybind11::arg("relu"), pybind11::arg("R"),
+          pybind11::arg("sy"), pybind11::arg("sx"), pybind11::arg("P"),
+          pybind11::arg("Q"));
+    m.def("bn_fold_eval_batch", &bn_fold_eval_batch, pybind11::arg("w_ptrs"),
+          pybind11::arg("b_ptrs"), pybind11::arg("rm_ptrs"),
+          pybind11::arg("rv_ptrs"), pybind11::arg("Cs"),
+          pybind11::arg("offs"), pybind11::arg("eps"), pybind11::arg("arena"),
+          pybind11::arg("max_c"),
+          "eval-mode BN scale/shift of every layer in one launch");
     m.def("conv_igemm_wgrad_into", &conv_igemm_wgrad_into);
     m.def("conv_igemm_wgrad", &conv_igemm_wgrad,
           "implicit-GEMM conv weight-grad (NHWC bf16, MFMA + tr16 reads)");

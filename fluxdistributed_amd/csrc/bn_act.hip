@@ -185,6 +185,29 @@ __global__ void bn_eval_finalize_kernel(float* __restrict__ ws,
     ws[C + c] = bn_shift_of(bias[c], mean, scale);
 }
 
+// Eval-mode fold of every BN layer of a model in one launch (inference
+// path): layer t = blockIdx.y writes scale[C] then shift[C] at arena +
+// offs[t], the ws layout of bn_eval_finalize_kernel and, through the shared
+// helpers, its exact values. Pointer tables as in wt_transpose_kernel. A
+// slice that would leave the arena is skipped rather than trusted.
+__global__ __launch_bounds__(256) void bn_fold_eval_batch_kernel(
+    const long* __restrict__ w_ptrs, const long* __restrict__ b_ptrs,
+    const long* __restrict__ rm_ptrs, const long* __restrict__ rv_ptrs,
+    const int* __restrict__ Cs, const long* __restrict__ offs,
+    const float* __restrict__ eps, float* __restrict__ arena,
+    long arena_len) {
+    const int t = blockIdx.y;
+    const int C = Cs[t];
+    const long off = offs[t];
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C || off < 0 || off + 2L * C > arena_len) return;
+    const float invstd = rsqrtf(((const float*)rv_ptrs[t])[c] + eps[t]);
+    const float scale = bn_scale_of(((const float*)w_ptrs[t])[c], invstd);
+    arena[off + c] = scale;
+    arena[off + C + c] = bn_shift_of(((const float*)b_ptrs[t])[c],
+                                     ((const float*)rm_ptrs[t])[c], scale);
+}
+
 template <typename T, int V, bool RELU, bool RES>
 __global__ void bn_apply_kernel(const T* __restrict__ x,
                                 const T* __restrict__ res, T* __restrict__ out,
@@ -379,6 +402,17 @@ void bn_eval_finalize_launch(float* ws, const float* weight,
     hipLaunchKernelGGL(bn_eval_finalize_kernel, dim3((C + 255) / 256),
                        dim3(256), 0, s, ws, weight, bias, running_mean,
                        running_var, save_mean, save_invstd, C, eps);
+}
+
+void bn_fold_eval_batch_launch(const long* w_ptrs, const long* b_ptrs,
+                               const long* rm_ptrs, const long* rv_ptrs,
+                               const int* Cs, const long* offs,
+                               const float* eps, float* arena, long arena_len,
+                               int nlayers, int max_c, hipStream_t s) {
+    dim3 grid((unsigned)((max_c + 255) / 256), (unsigned)nlayers);
+    hipLaunchKernelGGL(bn_fold_eval_batch_kernel, grid, dim3(256), 0, s,
+                       w_ptrs, b_ptrs, rm_ptrs, rv_ptrs, Cs, offs, eps, arena,
+                       arena_len);
 }
 
 void bn_apply_launch(const void* x, const void* residual, void* out,

@@ -30,9 +30,11 @@
 // Each tile has a second config for grids big enough to fill it: BK=32
 // K-steps on a 3-buffer counted ring (3x16 KiB at 3 blocks/CU, 3x20 KiB at
 // 2), chosen in conv_dispatch. Kernels in this file: conv_igemm_kernel
-// fwd+dgrad x 2 tiles x {BK64 2-buf, BK32 3-ring} (8) + the stem (1),
-// conv_wgrad_kernel FT2 / FT2-stem / FT4 (3), conv_skcombine_kernel,
-// wt_transpose_kernel. Variants that were measured and rejected are
+// fwd+dgrad x 2 tiles x {BK64 2-buf, BK32 3-ring} (8) + the stem (1), the
+// four fwd configs and the stem once more with the inference epilogue
+// (EpiInfer: eval BN + residual + ReLU before the single bf16 round),
+// conv_wgrad_kernel FT2 / FT2-stem / FT4 (3), conv_skcombine_kernel (plain
+// and EpiInfer), wt_transpose_kernel. Variants that were measured and rejected are
 // recorded in profiles/ab_conv8.md, profiles/ab_bigtile.md and
 // docs/wgrad_study.md, not kept here.
 // fp32 accumulate, bf16 store. Staging source offsets advance
@@ -79,9 +81,24 @@ enum ConvMode { CONV_FWD = 0, CONV_DGRAD = 1, CONV_STEM = 2 };
 
 constexpr int BK = 64;
 
+// Inference epilogue (eval BatchNorm + residual + ReLU on the fp32
+// accumulator, one bf16 round). Passed to conv_igemm_kernel /
+// conv_skcombine_kernel as the optional trailing EPI argument; the
+// training instantiations pass none, so their code and argument lists
+// are those of a kernel without it.
+struct EpiInfer {
+    const float* scale;                  // [OC]
+    const float* shift;                  // [OC]
+    const unsigned short* residual;      // output's layout, or null
+    int relu;
+};
+template <class E>
+__device__ __forceinline__ const E& epi_of(const E& e) { return e; }
+
 // NW = waves per block = (BM/64)*(BN/64): 4 for both the 128x128 and the
 // 256x64 config (256 threads, at least 2 blocks/CU).
-template <int MODE, int BM, int BN, int WN, int NBUF = 2, int BKT = BK>
+template <int MODE, int BM, int BN, int WN, int NBUF = 2, int BKT = BK,
+          class... EPI>
 __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64,
                              512 / ((BM / 64) * (BN / 64) * 64))
 void conv_igemm_kernel(
@@ -105,7 +122,12 @@ void conv_igemm_kernel(
            the result before the store — the residual-junction grad
            (d/d identity) fused into dx so autograd's separate
            CUDAFunctor_add pass disappears (ops/conv.py junction stash) */
+    ,
+    EPI... epi /* none (training) or one EpiInfer (fwd/stem inference) */
     ) {
+    static_assert(sizeof...(EPI) <= 1, "at most one epilogue functor");
+    constexpr bool FUSED = sizeof...(EPI) == 1;
+    static_assert(!FUSED || MODE != CONV_DGRAD, "inference epilogue is fwd");
     constexpr int NW = (BM / 64) * (BN / 64);   // waves per block
     constexpr int A_ELEMS = BM * BKT;
     constexpr int B_ELEMS = BN * BKT;
@@ -357,6 +379,71 @@ void conv_igemm_kernel(
     const int fcol = lane & 15, frow0 = (lane >> 4) * 4;
     float ssum[4] = {0.f, 0.f, 0.f, 0.f};   // per-ni channel sums (rounded y)
     float sq[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (FUSED) {
+        // y = bf16(relu(affine(acc) + residual)), LDS-staged: the wave's
+        // 64x64 fp32 tile goes through the staging LDS in two 32-row
+        // passes (34 KiB per block, inside every config's allocation), then
+        // every lane handles 8 consecutive channels of a row: 16-B residual
+        // read, 16-B store. Row stride 68 floats: the four rows a fragment
+        // write touches land on distinct 16-bank groups. (Storing in
+        // fragment order, 2 B per lane, measured slower on every shape and
+        // slower than the unfused pair with a residual:
+        // profiles/infer_fused.md.)
+        const auto& e = epi_of(epi...);
+        constexpr int SROW = 68;
+        static_assert(NW * 32 * SROW * 4 <= NBUF * BUF_ELEMS * 2,
+                      "staging passes must fit the block's own LDS");
+        float* st = (float*)lds + wid * (32 * SROW);
+        const int cg = lane & 7, rr = lane >> 3;
+        const int cbase = n0 + wn * 64 + cg * 8;
+        const float4 s0 = *(const float4*)(e.scale + cbase);
+        const float4 s1 = *(const float4*)(e.scale + cbase + 4);
+        const float4 h0 = *(const float4*)(e.shift + cbase);
+        const float4 h1 = *(const float4*)(e.shift + cbase + 4);
+        const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+        const float sh[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+        #pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            // every wave has read its last fragments (first pass) / its
+            // staged rows (second pass) before the LDS is overwritten
+            __syncthreads();
+            #pragma unroll
+            for (int mi2 = 0; mi2 < 2; ++mi2)
+                #pragma unroll
+                for (int ni = 0; ni < 4; ++ni)
+                    #pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        st[(mi2 * 16 + frow0 + j) * SROW + ni * 16 + fcol] =
+                            acc[half * 2 + mi2][ni][j];
+            __syncthreads();
+            #pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                const int lr = it * 8 + rr;
+                const long m = m0 + wm * 64 + half * 32 + lr;
+                if (m >= M) continue;
+                const float* sp = st + lr * SROW + cg * 8;
+                const float4 a0 = *(const float4*)sp;
+                const float4 a1 = *(const float4*)(sp + 4);
+                float v[8] = {a0.x, a0.y, a0.z, a0.w,
+                              a1.x, a1.y, a1.z, a1.w};
+                const long o = m * OC + cbase;
+                float rf[8];
+                if (e.residual)
+                    unpack_f32<unsigned short, 8>(
+                        *(const uint4*)(e.residual + o), rf);
+                unsigned short ov[8];
+                #pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    float t = bn_affine(v[k], sc[k], sh[k]);
+                    if (e.residual) t += rf[k];
+                    if (e.relu) t = fmaxf(t, 0.f);
+                    ov[k] = f32_to_bf16bits(t);
+                }
+                *(uint4*)(out + o) = *(uint4*)ov;
+            }
+        }
+        return;
+    }
     #pragma unroll
     for (int mi = 0; mi < 4; ++mi) {
         #pragma unroll
@@ -437,13 +524,14 @@ void conv_igemm_kernel(
     }
 }
 
-template <int MODE, int BM, int BN, int WN, int NBUF = 2, int BKT = BK>
+template <int MODE, int BM, int BN, int WN, int NBUF = 2, int BKT = BK,
+          class... EPI>
 static void launch_cfg(const void* src, const void* wgt, void* out,
                        int N, int H, int W, int C, int K, int P, int Q,
                        int R, int S, int sy, int sx, int py, int px,
                        hipStream_t stream, float* stats = nullptr,
                        float* skpart = nullptr, int SK = 1,
-                       const void* accsrc = nullptr) {
+                       const void* accsrc = nullptr, EPI... epi) {
     const int OC = (MODE == CONV_DGRAD) ? C : K;
     const long M = (MODE != CONV_DGRAD)
         ? (long)N * P * Q
@@ -456,25 +544,30 @@ static void launch_cfg(const void* src, const void* wgt, void* out,
     if (shmem > 65536) {
         static bool raised = [] {
             hipFuncSetAttribute(
-                (const void*)&conv_igemm_kernel<MODE, BM, BN, WN, NBUF, BKT>,
+                (const void*)&conv_igemm_kernel<MODE, BM, BN, WN, NBUF, BKT,
+                                                EPI...>,
                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             return true;
         }();
         (void)raised;
     }
-    hipLaunchKernelGGL((conv_igemm_kernel<MODE, BM, BN, WN, NBUF, BKT>), grid,
-                       dim3(NTHREADS), shmem, stream,
+    hipLaunchKernelGGL((conv_igemm_kernel<MODE, BM, BN, WN, NBUF, BKT, EPI...>),
+                       grid, dim3(NTHREADS), shmem, stream,
                        (const unsigned short*)src,
                        (const unsigned short*)wgt, (unsigned short*)out,
                        N, H, W, C, K, P, Q, R, S, sy, sx, py, px, stats,
-                       skpart, SK, (const unsigned short*)accsrc);
+                       skpart, SK, (const unsigned short*)accsrc, epi...);
 }
 
 // ---- split-K combine: y = bf16(sum_sk part) (+ BN stats partials) --------
+// EPI as in conv_igemm_kernel: with one EpiInfer the folded fp32 sum goes
+// through the inference epilogue before its single bf16 round.
+template <class... EPI>
 __global__ __launch_bounds__(256) void conv_skcombine_kernel(
     const float* __restrict__ part, unsigned short* __restrict__ y,
     float* __restrict__ stats, long M, int OC, int SK,
-    const unsigned short* __restrict__ accsrc) {
+    const unsigned short* __restrict__ accsrc, EPI... epi) {
+    static_assert(sizeof...(EPI) <= 1, "at most one epilogue functor");
     __shared__ float smem[2048];          // 256 threads x 8 lanes
     const int V = 8;
     const int tpr = OC / V;               // threads per row (OC <= 2048)
@@ -496,6 +589,29 @@ __global__ __launch_bounds__(256) void conv_skcombine_kernel(
             float4 b = *(const float4*)(p + 4);
             v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w;
             v[4] += b.x; v[5] += b.y; v[6] += b.z; v[7] += b.w;
+        }
+        if constexpr (sizeof...(EPI) == 1) {
+            const auto& e = epi_of(epi...);
+            const float4 s0 = *(const float4*)(e.scale + c0);
+            const float4 s1 = *(const float4*)(e.scale + c0 + 4);
+            const float4 h0 = *(const float4*)(e.shift + c0);
+            const float4 h1 = *(const float4*)(e.shift + c0 + 4);
+            const float sc[V] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+            const float sh[V] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+            float rf[V];
+            if (e.residual != nullptr)
+                unpack_f32<unsigned short, V>(
+                    *(const uint4*)(e.residual + r * OC + c0), rf);
+            unsigned short o[V];
+            #pragma unroll
+            for (int k = 0; k < V; ++k) {
+                float t = bn_affine(v[k], sc[k], sh[k]);
+                if (e.residual != nullptr) t += rf[k];
+                if (e.relu) t = fmaxf(t, 0.f);
+                o[k] = f32_to_bf16bits(t);
+            }
+            *(uint4*)(y + r * OC + c0) = *(uint4*)o;
+            continue;
         }
         if (accsrc != nullptr) {
             unsigned short av[V];
@@ -550,9 +666,20 @@ int conv_skcombine_blocks(long M, int OC) {
 void conv_skcombine_launch(const float* part, void* y, float* stats, long M,
                            int OC, int SK, int nblocks, hipStream_t stream,
                            const void* accsrc) {
-    hipLaunchKernelGGL(conv_skcombine_kernel, dim3(nblocks), dim3(256), 0,
+    hipLaunchKernelGGL(conv_skcombine_kernel<>, dim3(nblocks), dim3(256), 0,
                        stream, part, (unsigned short*)y, stats, M, OC, SK,
                        (const unsigned short*)accsrc);
+}
+
+void conv_skcombine_fused_launch(const float* part, void* y, long M, int OC,
+                                 int SK, int nblocks, const float* scale,
+                                 const float* shift, const void* residual,
+                                 bool relu, hipStream_t stream) {
+    const EpiInfer epi{scale, shift, (const unsigned short*)residual, relu};
+    hipLaunchKernelGGL(conv_skcombine_kernel<EpiInfer>, dim3(nblocks),
+                       dim3(256), 0, stream, part, (unsigned short*)y,
+                       (float*)nullptr, M, OC, SK,
+                       (const unsigned short*)nullptr, epi);
 }
 
 void conv_stem_fwd_launch(const void* src, const void* wgt, void* out,
@@ -564,6 +691,17 @@ void conv_stem_fwd_launch(const void* src, const void* wgt, void* out,
     launch_cfg<CONV_STEM, 256, 64, 1>(src, wgt, out, N, Hp, Wp, /*C=*/8, K,
                                       P, Q, R, /*S=*/1, sy, sx, 0, 0, stream,
                                       stats);
+}
+
+void conv_stem_fwd_fused_launch(const void* src, const void* wgt, void* out,
+                                int N, int Hp, int Wp, int K, int P, int Q,
+                                int R, int sy, int sx, const float* scale,
+                                const float* shift, bool relu,
+                                hipStream_t stream) {
+    const EpiInfer epi{scale, shift, nullptr, relu};
+    launch_cfg<CONV_STEM, 256, 64, 1, 2, BK, EpiInfer>(
+        src, wgt, out, N, Hp, Wp, /*C=*/8, K, P, Q, R, /*S=*/1, sy, sx, 0, 0,
+        stream, nullptr, nullptr, 1, nullptr, epi);
 }
 
 static bool conv_bk32() {
@@ -612,12 +750,19 @@ void conv_igemm_plan(long M, int OC, long T, int zbase,
     }
 }
 
-template <int MODE>
+// The BK32 rings need the grid to fill their blocks/CU: >= ~576 blocks at
+// 3 blocks/CU (128x128), >= 512 at 2 (256x64); below that the lost
+// per-block depth outweighs the extra overlap.
+bool conv_igemm_ring(long blocks, int bn) {
+    return conv_bk32() && blocks >= (bn == 128 ? 576 : 512);
+}
+
+template <int MODE, class... EPI>
 static void conv_dispatch(const void* src, const void* wgt, void* out,
                           int N, int H, int W, int C, int K, int P, int Q,
                           int R, int S, int sy, int sx, int py, int px,
                           hipStream_t stream, float* stats, float* skpart,
-                          int SK, const void* accsrc) {
+                          int SK, const void* accsrc, EPI... epi) {
     constexpr bool dgrad = MODE == CONV_DGRAD;
     const int OC = dgrad ? C : K;
     const long Mv = !dgrad
@@ -627,27 +772,24 @@ static void conv_dispatch(const void* src, const void* wgt, void* out,
     int BM, BN;
     conv_tile(OC, &BM, &BN);
     const long blocks = ((Mv + BM - 1) / BM) * (OC / BN) * zbase * SK;
-    // the BK32 rings need the grid to fill their blocks/CU: >= ~576 blocks
-    // at 3 blocks/CU (128x128), >= 512 at 2 (256x64); below that the lost
-    // per-block depth outweighs the extra overlap
     if (BN == 128) {
-        if (conv_bk32() && blocks >= 576)
-            launch_cfg<MODE, 128, 128, 2, 3, 32>(
+        if (conv_igemm_ring(blocks, BN))
+            launch_cfg<MODE, 128, 128, 2, 3, 32, EPI...>(
                 src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
-                stream, stats, skpart, SK, accsrc);
+                stream, stats, skpart, SK, accsrc, epi...);
         else
-            launch_cfg<MODE, 128, 128, 2>(
+            launch_cfg<MODE, 128, 128, 2, 2, BK, EPI...>(
                 src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
-                stream, stats, skpart, SK, accsrc);
+                stream, stats, skpart, SK, accsrc, epi...);
     } else {
-        if (conv_bk32() && blocks >= 512)
-            launch_cfg<MODE, 256, 64, 1, 3, 32>(
+        if (conv_igemm_ring(blocks, BN))
+            launch_cfg<MODE, 256, 64, 1, 3, 32, EPI...>(
                 src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
-                stream, stats, skpart, SK, accsrc);
+                stream, stats, skpart, SK, accsrc, epi...);
         else
-            launch_cfg<MODE, 256, 64, 1>(
+            launch_cfg<MODE, 256, 64, 1, 2, BK, EPI...>(
                 src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
-                stream, stats, skpart, SK, accsrc);
+                stream, stats, skpart, SK, accsrc, epi...);
     }
 }
 
@@ -664,6 +806,20 @@ void conv_igemm_launch(const void* src, const void* wgt, void* out,
         conv_dispatch<CONV_FWD>(src, wgt, out, N, H, W, C, K, P, Q, R, S,
                                 sy, sx, py, px, stream, stats, skpart, SK,
                                 accsrc);
+}
+
+// forward with the inference epilogue (SK == 1 shapes; split-K shapes run
+// the plain forward into fp32 partials and conv_skcombine_fused_launch)
+void conv_igemm_fwd_fused_launch(const void* src, const void* wgt, void* out,
+                                 int N, int H, int W, int C, int K, int P,
+                                 int Q, int R, int S, int sy, int sx, int py,
+                                 int px, const float* scale,
+                                 const float* shift, const void* residual,
+                                 bool relu, hipStream_t stream) {
+    const EpiInfer epi{scale, shift, (const unsigned short*)residual, relu};
+    conv_dispatch<CONV_FWD, EpiInfer>(src, wgt, out, N, H, W, C, K, P, Q, R,
+                                      S, sy, sx, py, px, stream, nullptr,
+                                      nullptr, 1, nullptr, epi);
 }
 
 // ---- batched conv-weight transpose ----------------------------------------

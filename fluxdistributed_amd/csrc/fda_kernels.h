@@ -75,6 +75,14 @@ void bn_eval_finalize_launch(float* ws, const float* weight,
 void bn_apply_launch(const void* x, const void* residual, void* out,
                      const float* ws /*scale/shift*/, int64_t rows, int C,
                      bool relu, DT dt, hipStream_t s);
+// eval fold of all BN layers of a model in one launch (device pointer
+// tables): layer t writes scale[Cs[t]] then shift[Cs[t]] at arena + offs[t],
+// bit-equal to bn_eval_finalize_launch's ws
+void bn_fold_eval_batch_launch(const long* w_ptrs, const long* b_ptrs,
+                               const long* rm_ptrs, const long* rv_ptrs,
+                               const int* Cs, const long* offs,
+                               const float* eps, float* arena, long arena_len,
+                               int nlayers, int max_c, hipStream_t s);
 
 // backward. ws is 2*C floats: [0,C) k1 = sum_g/m  [C,2C) k2 = sum_g_xhat/m
 // (both 0 in eval mode).
@@ -152,6 +160,10 @@ void conv_igemm_launch(const void* src, const void* wgt, void* out,
 void conv_igemm_plan(long M, int OC, long T, int zbase,
                      int* bm, int* bn, int* sk);
 
+// True when a launch of `blocks` blocks (all z and split-K slices counted)
+// with tile width bn takes the BK32 3-buffer ring instead of BK64 2-buffer.
+bool conv_igemm_ring(long blocks, int bn);
+
 // split-K combine: y = bf16(sum over SK fp32 partials) + optional BN
 // stats partials ([nblocks][2][OC])
 int conv_skcombine_blocks(long M, int OC);
@@ -167,6 +179,28 @@ void conv_stem_fwd_launch(const void* src, const void* wgt, void* out,
 void conv_stem_wgrad_launch(const void* dy, const void* x, float* ws,
                             int N, int Hp, int Wp, int K, int P, int Q,
                             int R, int sy, int sx, hipStream_t stream);
+
+// Inference forward: eval BN + residual + ReLU in the conv epilogue,
+//   y = bf16(relu(fma(acc, scale[k], shift[k]) + residual[m][k]))
+// from the fp32 accumulator, rounded once. scale/shift: K floats; residual:
+// bf16 in y's layout or null. The fwd launcher serves SK == 1 plans; for
+// SK > 1 run conv_igemm_launch into fp32 partials and fold them with
+// conv_skcombine_fused_launch, which applies the same epilogue.
+void conv_igemm_fwd_fused_launch(const void* src, const void* wgt, void* out,
+                                 int N, int H, int W, int C, int K, int P,
+                                 int Q, int R, int S, int sy, int sx, int py,
+                                 int px, const float* scale,
+                                 const float* shift, const void* residual,
+                                 bool relu, hipStream_t stream);
+void conv_skcombine_fused_launch(const float* part, void* y, long M, int OC,
+                                 int SK, int nblocks, const float* scale,
+                                 const float* shift, const void* residual,
+                                 bool relu, hipStream_t stream);
+void conv_stem_fwd_fused_launch(const void* src, const void* wgt, void* out,
+                                int N, int Hp, int Wp, int K, int P, int Q,
+                                int R, int sy, int sx, const float* scale,
+                                const float* shift, bool relu,
+                                hipStream_t stream);
 
 // wgrad: ws[K][RS*C] fp32 (pre-zeroed) += dy^T @ im2col(x), atomic chunks.
 void conv_wgrad_launch(const void* dy, const void* x, float* ws,

@@ -107,6 +107,7 @@ def syncgrads_worker(
     checkpoint_dir: str = "weights",
     should_stop: Optional[Callable[[int], bool]] = None,
     bucket_cap_mb: float = 25.0,
+    fused_eval: bool = False,
 ):
     """Per-rank training loop — the `getgrads` worker + `syncgrads` reducer
     of the reference collapsed into symmetric all-reduce ranks
@@ -142,7 +143,8 @@ def syncgrads_worker(
             from .task_ddp import log_loss_and_acc, Replica
 
             dev = x.device if x.is_cuda else "cpu"
-            log_loss_and_acc(loss_fn, Replica(0, dev, model, optimizer), val)
+            log_loss_and_acc(loss_fn, Replica(0, dev, model, optimizer), val,
+                             fused=fused_eval)
         if checkpoint_every and (step + 1) % checkpoint_every == 0 and rank == 0:
             from ..utils.checkpoint import save_checkpoint
 

@@ -156,11 +156,14 @@ def train(
     val_every: int = 50,
     batches: Optional[Callable[[int], Sequence]] = None,
     on_cycle_end: Optional[Callable[[int, TrainState], None]] = None,
+    fused_eval: bool = False,
 ):
     """Main synchronous loop (/root/reference/src/ddp_tasks.jl:174-247).
 
     `batches(j)` may supply the per-replica batch list for step j (used by
     tests to drive exact shards); otherwise each replica's loader is used.
+    `fused_eval` runs the periodic validation on the fused inference path
+    (see log_loss_and_acc).
     """
     reps = state.replicas
     for j in range(steps):
@@ -225,7 +228,7 @@ def train(
             log.info("cycle %d loss=%.4f imgs/s=%.1f", state.cycles,
                      sum(lv) / max(len(lv), 1), state.throughput.rate())
         if val is not None and val_every and (j + 1) % val_every == 0:
-            log_loss_and_acc(loss_fn, reps[0], val)
+            log_loss_and_acc(loss_fn, reps[0], val, fused=fused_eval)
         if sched is not None:
             sched(state.cycles)
         if on_cycle_end is not None:
@@ -234,19 +237,31 @@ def train(
     return [(r.device, r.model) for r in reps]
 
 
-def log_loss_and_acc(loss_fn, replica: Replica, val, ks=(1, 5, 10)):
+def log_loss_and_acc(loss_fn, replica: Replica, val, ks=(1, 5, 10),
+                     fused: bool = False):
     """Eval loss + top-k accuracy on the first replica
-    (/root/reference/src/ddp_tasks.jl:128-140)."""
+    (/root/reference/src/ddp_tasks.jl:128-140).
+
+    `fused=True` runs the forward through `compile_for_inference`: conv + BN
+    (+ residual + ReLU) as one kernel on the GPU, rounded once instead of
+    twice, so logits differ from the default path within bf16 rounding. The
+    model's mode is not touched on that path."""
     xv, yv = val
     model = replica.model
     was_training = model.training
-    model.eval()
+    if fused:
+        from ..inference import compile_for_inference
+
+        forward = compile_for_inference(model)
+    else:
+        model.eval()
+        forward = model
     with torch.no_grad(), device_ctx(replica.device):
         xd = to_device(xv, replica.device)
-        out = model(xd).float().cpu()
+        out = forward(xd).float().cpu()
         loss = float(loss_fn(out, yv))
         accs = {k: topkaccuracy(out, yv, k=k) for k in ks}
-    if was_training:
+    if was_training and not fused:
         model.train()
     log.info("val loss=%.4f " + " ".join(f"top{k}={accs[k]:.3f}" for k in ks), loss)
     return loss, accs

@@ -64,6 +64,9 @@ def parse_args():
     p.add_argument("--buffersize", type=int, default=5)
     p.add_argument("--val-every", type=int, default=50)
     p.add_argument("--log-every", type=int, default=10)
+    p.add_argument("--fused-eval", action="store_true",
+                   help="run validation forwards on the fused inference path "
+                        "(conv+BN+residual+ReLU in one kernel)")
     p.add_argument("--checkpoint-every", type=int, default=0)
     p.add_argument("--checkpoint-dir", default="weights")
     p.add_argument("--resume", default=None)
@@ -169,7 +172,7 @@ def run_task(args):
 
     results = train(logit_cross_entropy, st, steps=args.steps,
                     log_every=args.log_every, val_every=args.val_every,
-                    on_cycle_end=on_cycle_end)
+                    on_cycle_end=on_cycle_end, fused_eval=args.fused_eval)
     log.info("done: %d cycles, %d missed; timers=%s", st.cycles, st.num_missed,
              st.timers.summary())
     r = st.replicas[0]
@@ -199,7 +202,7 @@ def run_process(args):
     model_, opt_, stats = syncgrads_worker(
         model, opt, logit_cross_entropy, loader, steps=args.steps,
         checkpoint_every=args.checkpoint_every,
-        checkpoint_dir=args.checkpoint_dir,
+        checkpoint_dir=args.checkpoint_dir, fused_eval=args.fused_eval,
     )
     if rank == 0:
         log.info("done: %s", stats)
