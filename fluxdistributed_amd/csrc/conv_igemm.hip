@@ -43,7 +43,12 @@
 // partials of the rounded output for the downstream BatchNorm (`stats`),
 // and small-M deep-K shapes split the K loop over blockIdx.z into fp32
 // partials (`skpart`) folded by conv_skcombine_kernel — layer4-sized
-// grids otherwise fill only ~30% of the 256 CUs.
+// grids otherwise fill only ~30% of the 256 CUs. A non-split-K dgrad
+// stores dx (and reads the deferred junction gradient `accsrc`) through
+// the LDS staging of the inference epilogue, 16 B per lane; the forward
+// and stem training epilogues stay in fragment order, since they read
+// nothing and take their stats from the fragment registers
+// (profiles/step_profile_r4.md).
 //
 // This file also contains: the CONV_STEM mode (small-C stems on a
 // channel-padded C=8 image, r-only tap loop), the wgrad kernel
@@ -444,44 +449,103 @@ void conv_igemm_kernel(
         }
         return;
     }
+    if constexpr (MODE == CONV_DGRAD) {
+        if (skpart == nullptr) {
+            // dx = bf16(acc + accsrc), staged through the LDS exactly like
+            // the inference epilogue above (two 32-row passes, row stride
+            // 68 floats): every lane then owns 8 consecutive channels of a
+            // row, reads the deferred junction grad as one 16-B load and
+            // stores 16 B. Per element the arithmetic is that of the
+            // fragment-order form it replaces (one fp32 add, one round),
+            // so dx is bit-identical to it. The row's pixel address is
+            // computed per row, which is all the stride-2 parity classes
+            // need; a class with no filter tap (1x1 stride 2) stores its
+            // zeros 16 B at a time.
+            constexpr int SROW = 68;
+            static_assert(NW * 32 * SROW * 4 <= NBUF * BUF_ELEMS * 2,
+                          "staging passes must fit the block's own LDS");
+            float* st = (float*)lds + wid * (32 * SROW);
+            const int cg = lane & 7, rr = lane >> 3;
+            const int cbase = n0 + wn * 64 + cg * 8;
+            #pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                // every wave has read its last fragments (first pass) / its
+                // staged rows (second pass) before the LDS is overwritten
+                __syncthreads();
+                #pragma unroll
+                for (int mi2 = 0; mi2 < 2; ++mi2)
+                    #pragma unroll
+                    for (int ni = 0; ni < 4; ++ni)
+                        #pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            st[(mi2 * 16 + frow0 + j) * SROW + ni * 16 + fcol] =
+                                acc[half * 2 + mi2][ni][j];
+                __syncthreads();
+                #pragma unroll
+                for (int it = 0; it < 4; ++it) {
+                    const int lr = it * 8 + rr;
+                    const long m = m0 + wm * 64 + half * 32 + lr;
+                    if (m >= M) continue;
+                    const int ww = (int)(m % OW);
+                    const int hh = (int)((m / OW) % OH);
+                    const int n = (int)(m / ((long)OW * OH));
+                    const long o = (((long)n * H + a + (long)sy * hh) * W + b +
+                                    (long)sx * ww) * C + cbase;
+                    const float* sp = st + lr * SROW + cg * 8;
+                    const float4 a0 = *(const float4*)sp;
+                    const float4 a1 = *(const float4*)(sp + 4);
+                    float v[8] = {a0.x, a0.y, a0.z, a0.w,
+                                  a1.x, a1.y, a1.z, a1.w};
+                    if (accsrc != nullptr) {
+                        float rf[8];
+                        unpack_f32<unsigned short, 8>(
+                            *(const uint4*)(accsrc + o), rf);
+                        #pragma unroll
+                        for (int k = 0; k < 8; ++k) v[k] += rf[k];
+                    }
+                    unsigned short ov[8];
+                    #pragma unroll
+                    for (int k = 0; k < 8; ++k) ov[k] = f32_to_bf16bits(v[k]);
+                    *(uint4*)(out + o) = *(uint4*)ov;
+                }
+            }
+            return;
+        }
+    }
     #pragma unroll
     for (int mi = 0; mi < 4; ++mi) {
         #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const long m = m0 + wm * 64 + mi * 16 + frow0 + j;
             if (m >= M) continue;
-            long obase;
-            if (MODE != CONV_DGRAD) {
-                obase = m * OC;
-            } else {
-                const int ww = (int)(m % OW);
-                const int hh = (int)((m / OW) % OH);
-                const int n = (int)(m / ((long)OW * OH));
-                obase = (((long)n * H + a + (long)sy * hh) * W + b +
-                         (long)sx * ww) * C;
-            }
+            const long obase = m * OC;
             if (skpart != nullptr) {
                 // split-K: fp32 partials, linear by m (the dgrad split path
-                // is stride-1 only, where obase == m*OC)
+                // is stride-1 only, where its pixel offset is m*OC too)
                 float* prow = skpart + ((long)sk * M + m) * OC + n0 + wn * 64;
                 #pragma unroll
                 for (int ni = 0; ni < 4; ++ni)
                     prow[ni * 16 + fcol] = acc[mi][ni][j];
                 continue;
             }
-            unsigned short* orow = out + obase + n0 + wn * 64;
-            const unsigned short* arow =
-                accsrc ? accsrc + obase + n0 + wn * 64 : nullptr;
-            #pragma unroll
-            for (int ni = 0; ni < 4; ++ni) {
-                float v = acc[mi][ni][j];
-                if (arow) v += bf16bits_to_f32(arow[ni * 16 + fcol]);
-                const unsigned short us = f32_to_bf16bits(v);
-                orow[ni * 16 + fcol] = us;
-                if (MODE != CONV_DGRAD && stats != nullptr) {
-                    const float v = bf16bits_to_f32(us);
-                    ssum[ni] += v;
-                    sq[ni] += v * v;
+            // fwd / stem only from here on: a non-split dgrad left above.
+            // Fragment order, 2 B per lane: these read nothing, and their
+            // stats come straight from the fragment registers.
+            if constexpr (MODE != CONV_DGRAD) {
+                unsigned short* orow = out + obase + n0 + wn * 64;
+                const unsigned short* arow =
+                    accsrc ? accsrc + obase + n0 + wn * 64 : nullptr;
+                #pragma unroll
+                for (int ni = 0; ni < 4; ++ni) {
+                    float v = acc[mi][ni][j];
+                    if (arow) v += bf16bits_to_f32(arow[ni * 16 + fcol]);
+                    const unsigned short us = f32_to_bf16bits(v);
+                    orow[ni * 16 + fcol] = us;
+                    if (stats != nullptr) {
+                        const float v = bf16bits_to_f32(us);
+                        ssum[ni] += v;
+                        sq[ni] += v * v;
+                    }
                 }
             }
         }

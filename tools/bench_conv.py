@@ -4,6 +4,7 @@
 Times fwd and dgrad for every ResNet-34 bs-96 body shape; prints a table
 with effective TFLOP/s. Run on a GPU box:
     python tools/bench_conv.py [--batch 96] [--iters 50]
+    python tools/bench_conv.py --mode dgrad --iters 200   # dgrad arms only
 """
 
 import argparse
@@ -43,17 +44,79 @@ def timeit(fn, iters, warmup=10):
     return (time.perf_counter() - t0) / iters
 
 
+def event_us(fn, iters, warmup=10):
+    """Mean device time of one call in us (events around `iters` calls)."""
+    for _ in range(warmup):
+        fn()
+    e0 = torch.cuda.Event(enable_timing=True)
+    e1 = torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / iters
+
+
+def dgrad_arms(args):
+    """Input-grad arms: plain, and with the deferred junction gradient
+    (`accum`) added in the epilogue. Each figure is the median of
+    --repeats timed blocks, with their min..max as the run-to-run spread."""
+    C_ = require_native("conv_igemm_dgrad")
+    n = args.batch
+    print(f"# batch={n} dgrad, us per call: median (min..max) of "
+          f"{args.repeats} blocks of {args.iters} calls")
+    print(f"{'shape':34s} {'plain':>22s} {'with accum':>22s}")
+    shapes = SHAPES if args.only < 0 else [SHAPES[args.only]]
+    tot = [0.0, 0.0]
+    for (c, h, w, k, r, s, cnt) in shapes:
+        pad = r // 2
+        P, Q = (h + 2 * pad - r) // s + 1, (w + 2 * pad - r) // s + 1
+        gy = torch.randn(n, k, P, Q, device="cuda").bfloat16() \
+            .contiguous(memory_format=torch.channels_last)
+        wtt = torch.randn(r * r * c, k, device="cuda").bfloat16()
+        acc = torch.randn(n, c, h, w, device="cuda").bfloat16() \
+            .contiguous(memory_format=torch.channels_last)
+        arms = [
+            lambda: C_.conv_igemm_dgrad(gy, wtt, c, h, w, r, r, s, s, pad,
+                                        pad, None),
+            lambda: C_.conv_igemm_dgrad(gy, wtt, c, h, w, r, r, s, s, pad,
+                                        pad, acc),
+        ]
+        cells = []
+        # blocks of the arms in turn, so drift hits every arm alike
+        ts = [[] for _ in arms]
+        for _ in range(args.repeats):
+            for i, fn in enumerate(arms):
+                ts[i].append(event_us(fn, args.iters))
+        for i, t in enumerate(ts):
+            t.sort()
+            med = t[len(t) // 2]
+            tot[i] += med * cnt
+            cells.append(f"{med:7.1f} ({t[0]:.1f}..{t[-1]:.1f})")
+        name = f"{c}x{h}x{w} k{k} {r}x{r} s{s} x{cnt}"
+        print(f"{name:34s} {cells[0]:>22s} {cells[1]:>22s}")
+    print(f"{'TOTAL (weighted by layer count)':34s} {tot[0]:22.1f} {tot[1]:22.1f}")
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, default=96)
     p.add_argument("--iters", type=int, default=50)
-    p.add_argument("--mode", choices=["fwd", "dgrad", "both"], default="both")
+    p.add_argument("--repeats", type=int, default=5,
+                   help="timed blocks per arm (--mode dgrad)")
+    p.add_argument("--mode", choices=["fwd", "dgrad", "both"], default="both",
+                   help="dgrad: only the input-grad arms, plain and with "
+                        "accum, with their run-to-run spread")
     p.add_argument("--only", type=int, default=-1,
                    help="run only SHAPES[i] (for PMC profiling runs)")
     p.add_argument("--fda-only", action="store_true",
                    help="skip the library arms (clean kernel-trace)")
     args = p.parse_args()
     assert torch.cuda.is_available()
+    if args.mode == "dgrad":
+        return dgrad_arms(args)
     torch.backends.cudnn.benchmark = True
     C_ = require_native("conv_igemm_fwd")
     n = args.batch
