@@ -33,6 +33,7 @@ from .parallel.gradtree import (  # noqa: F401
     ensure_synced,
     check_nans,
 )
+from .parallel.flatsync import FlatGradReducer  # noqa: F401
 from .parallel.task_ddp import prepare_training, train, train_step  # noqa: F401
 from .data.imagenet import minibatch, minibatch_raw, train_solutions, labels  # noqa: F401
 from .data.preprocess import RawBatch, pack_images, preprocess_batch  # noqa: F401

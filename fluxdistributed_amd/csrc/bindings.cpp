@@ -507,6 +507,48 @@ void adam_step(at::Tensor P, at::Tensor G, at::Tensor M, at::Tensor V,
                           dt_of(P), cur_stream());
 }
 
+// Replica gradient mean, in place over the R flat G buffers of one dtype
+// group (parallel/flatsync.py). The kernel reads every buffer before it
+// writes any, per 16 B vector; an aliased pair would still race between
+// lanes, so overlapping byte ranges are refused.
+void grad_mean_multi(std::vector<at::Tensor> grads,
+                     c10::optional<at::Tensor> flag) {
+    const char* op = "grad_mean_multi";
+    const int64_t R = (int64_t)grads.size();
+    TORCH_CHECK(R >= 1 && R <= fda::GRAD_MEAN_MAX_R, op, ": needs 1..",
+                fda::GRAD_MEAN_MAX_R, " buffers, got ", R);
+    const at::Tensor& g0 = grads[0];
+    const DT dt = dt_of(g0);
+    const int vw = dt == DT::BF16 ? 8 : 4;
+    const int64_t n = g0.numel();
+    TORCH_CHECK(n % vw == 0, op, ": flat buffers must be padded to ", vw,
+                " elements, got ", n);
+    for (const auto& g : grads) {
+        TORCH_CHECK(g.dim() == 1, op, ": buffers must be 1-D");
+        check_flat(op, "every buffer", g, g0.scalar_type(), n);
+        TORCH_CHECK((uintptr_t)g.data_ptr() % 16 == 0, op,
+                    ": every buffer must be 16-byte aligned");
+    }
+    const int64_t bytes = n * (int64_t)g0.element_size();
+    for (int64_t i = 0; i < R; ++i)
+        for (int64_t j = i + 1; j < R; ++j) {
+            const char* a = (const char*)grads[i].data_ptr();
+            const char* b = (const char*)grads[j].data_ptr();
+            TORCH_CHECK(a + bytes <= b || b + bytes <= a, op, ": buffers ", i,
+                        " and ", j, " overlap (the in-place write would race)");
+        }
+    if (flag.has_value())
+        check_flat(op, "flag", *flag, at::kInt, 1);
+    // check_device, for a list: all on one GPU
+    for (const auto& g : grads) check_device(op, {g0, g});
+    if (flag.has_value()) check_device(op, {g0, *flag});
+    void* ptrs[fda::GRAD_MEAN_MAX_R];
+    for (int64_t i = 0; i < R; ++i) ptrs[i] = grads[i].data_ptr();
+    fda::grad_mean_multi_launch(
+        ptrs, (int)R, n, flag.has_value() ? flag->data_ptr<int>() : nullptr,
+        dt, cur_stream());
+}
+
 }  // namespace
 
 // ---- implicit-GEMM conv (NHWC bf16, conv_igemm.hip) -----------------------
@@ -1127,6 +1169,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gap_bwd", &gap_bwd);
     m.def("sgd_step", &sgd_step);
     m.def("adam_step", &adam_step);
+    m.def("grad_mean_multi", &grad_mean_multi, pybind11::arg("grads"),
+          pybind11::arg("flag") = pybind11::none(),
+          "in-place mean of R flat gradient buffers (fp32 sum, one round)");
     m.def("conv_igemm_fwd_stats", &conv_igemm_fwd_stats);
     m.def("conv_stem_fwd_stats", &conv_stem_fwd_stats);
     m.def("conv_igemm_fwd", &conv_igemm_fwd,

@@ -274,6 +274,81 @@ void adam_step_launch(void* P, const void* G, float* M, float* V, float* S,
     });
 }
 
+// --------------------------------------------------------------------------
+// Replica gradient mean for task-DDP (parallel/flatsync.py): the R flat G
+// buffers of one dtype group become their mean, in place, in one launch.
+//   mean = round(((g0 + g1) + ... + gR-1) / R)   fp32 sum in replica order,
+// one correctly rounded division, one round to the storage dtype; the same
+// 16 B then goes to all R buffers. The pointers travel by value in the
+// kernel arguments (no device table, no H2D copy; the launch stays
+// capturable) and R is a template parameter, so a lane issues its R loads
+// back to back before the first add and before any store. Bit-exact against
+// the torch definition: adds and one division only, nothing to contract.
+// --------------------------------------------------------------------------
+struct GradBufs { void* p[GRAD_MEAN_MAX_R]; };
+
+template <typename T, int V, int R>
+__global__ __launch_bounds__(256) void grad_mean_multi_kernel(
+    GradBufs bufs, int64_t n, int* __restrict__ nonfinite) {
+    const int64_t nv = n / V;
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        uint4 raw[R];
+        #pragma unroll
+        for (int r = 0; r < R; ++r) raw[r] = ((const uint4*)bufs.p[r])[i];
+        float acc[V];
+        unpack_f32<T, V>(raw[0], acc);
+        #pragma unroll
+        for (int r = 1; r < R; ++r) {
+            float f[V];
+            unpack_f32<T, V>(raw[r], f);
+            #pragma unroll
+            for (int k = 0; k < V; ++k) acc[k] += f[k];
+        }
+        T ov[V];
+        #pragma unroll
+        for (int k = 0; k < V; ++k) {
+            store_f32(ov + k, __fdiv_rn(acc[k], (float)R));
+            // Inf/NaN of the value as stored (all exponent bits set)
+            bad |= (__float_as_uint(load_f32(ov + k)) & 0x7f800000u) ==
+                   0x7f800000u;
+        }
+        const uint4 o = *(const uint4*)ov;
+        #pragma unroll
+        for (int r = 0; r < R; ++r) ((uint4*)bufs.p[r])[i] = o;
+    }
+    // failure case only: at most one vector atomic per lane, none otherwise
+    if (nonfinite != nullptr && bad) atomicOr(nonfinite, 1);
+}
+
+template <typename T, int V, int R>
+static void grad_mean_multi_dispatch(const GradBufs& bufs, int nbufs,
+                                     int64_t n, int* nonfinite,
+                                     hipStream_t s) {
+    if constexpr (R <= GRAD_MEAN_MAX_R) {
+        if (nbufs == R)
+            hipLaunchKernelGGL((grad_mean_multi_kernel<T, V, R>),
+                               dim3(grid_1d(n / V, 4096)), dim3(256), 0, s,
+                               bufs, n, nonfinite);
+        else
+            grad_mean_multi_dispatch<T, V, R + 1>(bufs, nbufs, n, nonfinite,
+                                                  s);
+    }
+}
+
+void grad_mean_multi_launch(void* const* bufs, int R, int64_t n,
+                            int* nonfinite, DT dt, hipStream_t s) {
+    if (R < 1 || R > GRAD_MEAN_MAX_R) return;  // the binding refuses these
+    GradBufs b{};
+    for (int r = 0; r < R; ++r) b.p[r] = bufs[r];
+    dispatch_dtype(dt, [&](auto t, auto v) {
+        using T = decltype(t);
+        constexpr int V = decltype(v)::value;
+        grad_mean_multi_dispatch<T, V, 1>(b, R, n, nonfinite, s);
+    });
+}
+
 // G_bf16 += cast(ws_f32): the direct-grad flush for one conv weight slice
 // (replaces an aten cast kernel + an AccumulateGrad add per layer).
 __global__ __launch_bounds__(256) void grad_accum_bf16_kernel(

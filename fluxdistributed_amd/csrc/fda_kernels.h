@@ -264,4 +264,14 @@ void adam_step_launch(void* P, const void* G, float* M, float* V, float* S,
                       float wd, float bc1, float bc2, bool has_master, DT dt,
                       hipStream_t s);
 
+// Replica gradient mean (task-DDP flat sync): bufs is a HOST array of R
+// device pointers (1 <= R <= GRAD_MEAN_MAX_R) to disjoint, 16 B-aligned flat
+// buffers of n elements, n % V == 0. Each becomes
+//   round(((b0 + b1) + ... + bR-1) / R),   fp32 sum, IEEE division, one round
+// in place. nonfinite (device int, may be null) is OR-ed with 1 when any
+// stored mean element is Inf/NaN.
+constexpr int GRAD_MEAN_MAX_R = 16;
+void grad_mean_multi_launch(void* const* bufs, int R, int64_t n,
+                            int* nonfinite, DT dt, hipStream_t s);
+
 }  // namespace fda

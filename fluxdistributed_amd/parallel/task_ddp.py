@@ -7,13 +7,23 @@ buffer, reduced to their mean, broadcast back, and each replica takes an
 identical optimizer step — fully synchronous SGD, math-equivalent to
 large-batch.
 
+Two gradient-sync modes (`prepare_training(grad_sync=...)`):
+- "tree" (default): the reference's leaf-by-leaf protocol. Each replica
+  owns a model-sized buffer tree on the first replica's device ("HOST" in
+  the reference, ddp_tasks.jl:250); grads are copied in per leaf, folded in
+  the parameter dtype, and copied back per leaf.
+- "flat": no buffer tree at all. The replicas' flat gradient buffers
+  (ops/fused_optim.py) become their mean in place, one kernel per dtype
+  group with fp32 accumulation and a single round (flatsync.py). Replicas on
+  other GPUs are staged through one flat row each on the first replica's
+  device.
+
 Differences from the reference (deliberate, MI355X-first):
 - replicas are keyed by index, not device object (a logical fan-out may put
   two replicas on one GPU — reference test/single_device.jl:127-133);
-- the buffer lives on the first replica's device ("HOST" in the reference,
-  ddp_tasks.jl:250) and buffer allocation is completed before return —
-  the reference's unawaited alloc tasks are a known latent race
-  (SURVEY.md "known reference bugs");
+- tree-mode buffer allocation is completed before return — the
+  reference's unawaited alloc tasks are a known latent race (SURVEY.md
+  "known reference bugs");
 - `num_missed` OOM counter actually increments (reference bug
   ddp_tasks.jl:180,240);
 - per-stage timers + images/sec (observability the reference lacks,
@@ -33,6 +43,7 @@ import torch
 from .gradtree import (
     destruct, grads_of, markbuffer_, getbuffer_, sync_buffer,
 )
+from .flatsync import FlatGradReducer
 from ..utils.device import device_ctx, synchronize, to_device, is_real_gpu
 from ..utils.timers import StageTimers, Throughput
 from ..utils.metrics import topkaccuracy
@@ -53,12 +64,15 @@ class Replica:
 @dataclass
 class TrainState:
     replicas: List[Replica]
-    buffer: Dict[int, dict]          # replica index -> GradTree on HOST device
+    buffer: Dict[int, dict]          # replica index -> GradTree on HOST
+                                     # device; {} in flat mode
     host_device: object
     cycles: int = 0
     num_missed: int = 0
     timers: StageTimers = field(default_factory=StageTimers)
     throughput: Throughput = field(default_factory=Throughput)
+    reducer: Optional[FlatGradReducer] = None   # set in flat mode
+    nonfinite_steps: int = 0         # flat mode: log points with Inf/NaN means
 
 
 def prepare_training(
@@ -69,8 +83,13 @@ def prepare_training(
     nsamples: int = 32,
     buffersize: int = 5,
     loader_factory: Optional[Callable] = None,
+    grad_sync: str = "tree",
 ) -> TrainState:
     """Replicate model + optimizer + loader per device; allocate grad buffers.
+
+    `grad_sync="flat"` allocates no buffer tree (`state.buffer == {}`) and
+    reduces the replicas' flat gradient buffers in place instead; it needs
+    flat optimizers with identical group layouts (flatsync.FlatGradReducer).
 
     Mirrors /root/reference/src/ddp_tasks.jl:249-289. `data` is a callable
     `data(nsamples) -> (x, y)` batch sampler (the reference's
@@ -82,6 +101,9 @@ def prepare_training(
     """
     from ..data.loader import PrefetchLoader
 
+    if grad_sync not in ("tree", "flat"):
+        raise ValueError(
+            f"grad_sync must be 'tree' or 'flat', got {grad_sync!r}")
     host = devices[0]
     if data is not None and not callable(data):
         per_replica = list(data)
@@ -105,6 +127,9 @@ def prepare_training(
             loader = fac(lambda n=nsamples, _fn=fn: _fn(n), dev)
         replicas.append(Replica(i, dev, m, opt, loader))
 
+    if grad_sync == "flat":
+        return TrainState(replicas=replicas, buffer={}, host_device=host,
+                          reducer=FlatGradReducer(replicas))
     buffer: Dict[int, dict] = {}
     with device_ctx(host):
         for r in replicas:
@@ -117,7 +142,8 @@ def prepare_training(
 
 def train_step(loss_fn, buffer, replica: Replica, x, y):
     """Forward+backward on one replica, then publish grads to its buffer slot
-    (/root/reference/src/ddp_tasks.jl:80-84)."""
+    (/root/reference/src/ddp_tasks.jl:80-84). In flat mode there are no
+    slots (`buffer == {}`): the gradients stay in the replica's flat G."""
     from ..ops.gradflush import pop_no_defer, push_no_defer
 
     with device_ctx(replica.device):
@@ -131,17 +157,20 @@ def train_step(loss_fn, buffer, replica: Replica, x, y):
             loss.backward()
         finally:
             pop_no_defer()
-        markbuffer_(buffer[replica.index], grads_of(replica.model))
+        if buffer:
+            markbuffer_(buffer[replica.index], grads_of(replica.model))
         synchronize(replica.device)
     return loss.detach()
 
 
 def update(replica: Replica, final):
     """Write reduced grads into the replica's grad memory and step
-    (/root/reference/src/ddp_tasks.jl:163-172)."""
+    (/root/reference/src/ddp_tasks.jl:163-172). `final=None`: the grad
+    memory already holds the mean (flat mode), so only the step runs."""
     with device_ctx(replica.device):
-        getbuffer_(grads_of(replica.model), final)
-        synchronize(replica.device)
+        if final is not None:
+            getbuffer_(grads_of(replica.model), final)
+            synchronize(replica.device)
         replica.optimizer.step()
         synchronize(replica.device)
 
@@ -208,7 +237,11 @@ def train(
             continue
 
         with state.timers.stage("allreduce"):
-            final = sync_buffer(state.buffer, average=True)
+            if state.reducer is not None:
+                state.reducer.reduce()
+                final = None
+            else:
+                final = sync_buffer(state.buffer, average=True)
 
         with state.timers.stage("optimizer"):
             uth = [
@@ -227,6 +260,12 @@ def train(
             lv = [float(l) for l in losses if l is not None]
             log.info("cycle %d loss=%.4f imgs/s=%.1f", state.cycles,
                      sum(lv) / max(len(lv), 1), state.throughput.rate())
+            # the loss read above has synchronized already
+            if state.reducer is not None and state.reducer.pop_nonfinite():
+                state.nonfinite_steps += 1
+                log.warning("non-finite gradient mean seen by cycle %d "
+                            "(nonfinite_steps=%d)", state.cycles,
+                            state.nonfinite_steps)
         if val is not None and val_every and (j + 1) % val_every == 0:
             log_loss_and_acc(loss_fn, reps[0], val, fused=fused_eval)
         if sched is not None:

@@ -67,6 +67,11 @@ def parse_args():
     p.add_argument("--fused-eval", action="store_true",
                    help="run validation forwards on the fused inference path "
                         "(conv+BN+residual+ReLU in one kernel)")
+    p.add_argument("--grad-sync", choices=["tree", "flat"], default="tree",
+                   help="task mode: 'tree' folds per-leaf buffer trees on the "
+                        "first device; 'flat' averages the replicas' flat "
+                        "gradient buffers in place in one kernel (fp32 "
+                        "accumulation, no buffer tree)")
     p.add_argument("--checkpoint-every", type=int, default=0)
     p.add_argument("--checkpoint-dir", default="weights")
     p.add_argument("--resume", default=None)
@@ -156,7 +161,7 @@ def run_task(args):
          for i in range(len(devices))],
         devices, make_opt_factory(args),
         nsamples=args.batch, buffersize=args.buffersize,
-        loader_factory=loader_factory,
+        loader_factory=loader_factory, grad_sync=args.grad_sync,
     )
     if args.resume:
         for r in st.replicas:
