@@ -27,7 +27,7 @@ std::pair<int64_t, int64_t> nhwc_rows(const at::Tensor& x) {
     return {x.size(0) * x.size(2) * x.size(3), x.size(1)};
 }
 
-// ---- operand checks for the non-conv entry points -------------------------
+// ---- operand checks --------------------------------------------------------
 // Every pointer a kernel receives is checked here first: a host tensor or a
 // short buffer would otherwise become a wild access on the GPU. Each entry
 // point makes its shape, dtype and layout checks first and calls
@@ -549,183 +549,221 @@ void grad_mean_multi(std::vector<at::Tensor> grads,
         dt, cur_stream());
 }
 
-}  // namespace
-
 // ---- implicit-GEMM conv (NHWC bf16, conv_igemm.hip) -----------------------
-// Tile geometry and split-K come from fda::conv_igemm_plan (the same
-// function the launcher obeys), so workspace shapes always match.
+// As above: shape, dtype, layout and geometry checks first, check_device
+// last, so every refusal can be exercised on a machine without a GPU.
 
-// Operand check shared by the five conv_igemm entry points. `act` is a 4-D
-// channels_last activation (x or dy); `other` is the second operand: a 4-D
-// channels_last tensor (w, or x for wgrad) or the 2-D contiguous
-// pre-transposed weight wt of dgrad. Both channel counts must be multiples
-// of 64.
-static void check_conv_operands(const at::Tensor& act, const at::Tensor& other,
-                                int64_t C, int64_t K) {
-    TORCH_CHECK(act.is_cuda() && other.is_cuda(),
-                "conv_igemm: device tensors required (a CPU tensor here "
-                "would fault the GPU with a host pointer)");
-    TORCH_CHECK(act.scalar_type() == at::kBFloat16 &&
-                other.scalar_type() == at::kBFloat16,
-                "conv_igemm: bf16 only");
-    TORCH_CHECK(act.dim() == 4 &&
-                act.is_contiguous(at::MemoryFormat::ChannelsLast),
-                "conv_igemm: activations must be 4-D channels_last");
-    TORCH_CHECK(other.dim() == 2
-                    ? other.is_contiguous()
-                    : other.dim() == 4 &&
-                      other.is_contiguous(at::MemoryFormat::ChannelsLast),
-                "conv_igemm: second operand must be 4-D channels_last, or "
-                "the 2-D contiguous transposed weight for dgrad");
-    TORCH_CHECK(C % 64 == 0 && K % 64 == 0,
-                "conv_igemm: C and K must be multiples of 64");
+void check_cl_bf16(const char* op, const char* name, const at::Tensor& t) {
+    TORCH_CHECK(t.dim() == 4 && t.scalar_type() == at::kBFloat16 &&
+                    t.is_contiguous(at::MemoryFormat::ChannelsLast),
+                op, ": ", name, " must be 4-D channels_last bf16");
 }
 
-// forward, optionally with per-m-tile BN partials [tiles][2][K] (sum/sumsq
-// of the rounded output) that feed bn_fwd_finalize_launch; the partials
-// tensor is undefined when want_stats is false.
-static std::tuple<at::Tensor, at::Tensor> conv_igemm_fwd_impl(
-    const at::Tensor& x, const at::Tensor& w, int64_t sy, int64_t sx,
-    int64_t py, int64_t px, bool want_stats) {
-    TORCH_CHECK(x.dim() == 4 && w.dim() == 4);
-    const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2),
-              W = (int)x.size(3);
-    const int K = (int)w.size(0), R = (int)w.size(2), S = (int)w.size(3);
-    check_conv_operands(x, w, C, K);
-    TORCH_CHECK((int)w.size(1) == C, "channel mismatch");
-    const int P = (H + 2 * (int)py - R) / (int)sy + 1;
-    const int Q = (W + 2 * (int)px - S) / (int)sx + 1;
-    auto y = at::empty({N, K, P, Q},
-                       x.options().memory_format(at::MemoryFormat::ChannelsLast));
-    const auto f32 = x.options().dtype(at::kFloat);
-    const long M = (long)N * P * Q;
-    int BM, BN, SK;
-    fda::conv_igemm_plan(M, K, (long)R * S * (C / 64), 1, &BM, &BN, &SK);
-    at::Tensor part;
-    if (SK > 1) {
-        // the combine kernel rounds to bf16 and writes the partials
-        auto skp = at::empty({(long)SK * M * K}, f32);
-        const int nb = fda::conv_skcombine_blocks(M, K);
-        if (want_stats) part = at::empty({nb, 2, K}, f32);
-        fda::conv_igemm_launch(x.data_ptr(), w.data_ptr(), y.data_ptr(),
-                               N, H, W, C, K, P, Q, R, S, (int)sy, (int)sx,
-                               (int)py, (int)px, /*dgrad=*/false,
-                               cur_stream(), nullptr, skp.data_ptr<float>(),
-                               SK);
-        fda::conv_skcombine_launch(skp.data_ptr<float>(), y.data_ptr(),
-                                   want_stats ? part.data_ptr<float>() : nullptr,
-                                   M, K, SK, nb, cur_stream());
-        return {y, part};
+// the kernels read `name` as 16-B vectors
+void check_aligned16(const char* op, const char* name, const at::Tensor& t) {
+    TORCH_CHECK((reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0, op,
+                ": ", name, " must be 16-byte aligned");
+}
+
+// The geometry of a conv_igemm call, checked, with the output size filled
+// in: x [N,C,H,W], w [K,C,R,S] in logical sizes.
+fda::ConvGeom conv_geometry(const char* op, int64_t N, int64_t C, int64_t H,
+                            int64_t W, int64_t K, int64_t R, int64_t S,
+                            int64_t sy, int64_t sx, int64_t py, int64_t px) {
+    TORCH_CHECK(C >= 64 && K >= 64 && C % 64 == 0 && K % 64 == 0, op,
+                ": C and K must be multiples of 64, got C=", C, " K=", K);
+    TORCH_CHECK(N >= 1 && sy >= 1 && sx >= 1 && py >= 0 && px >= 0, op,
+                ": bad stride/padding: need N >= 1, strides >= 1 and "
+                "paddings >= 0, got N=", N, " stride ", sy, "x", sx,
+                " padding ", py, "x", px);
+    TORCH_CHECK(R >= 1 && S >= 1 && H + 2 * py >= R && W + 2 * px >= S, op,
+                ": filter ", R, "x", S, " larger than the padded input ",
+                H + 2 * py, "x", W + 2 * px);
+    const int64_t P = (H + 2 * py - R) / sy + 1;
+    const int64_t Q = (W + 2 * px - S) / sx + 1;
+    return {(int)N, (int)H,  (int)W,  (int)C,  (int)K,  (int)P, (int)Q,
+            (int)R, (int)S, (int)sy, (int)sx, (int)py, (int)px};
+}
+
+// dy [N,K,P,Q] is the output gradient of geometry g
+void check_dy(const char* op, const at::Tensor& dy, const fda::ConvGeom& g) {
+    TORCH_CHECK(dy.size(2) == g.P && dy.size(3) == g.Q, op, ": dy is ",
+                dy.size(2), "x", dy.size(3), " but this input, filter, "
+                "stride and padding give an output of ", g.P, "x", g.Q);
+}
+
+// scale/shift of the inference epilogue: K floats each
+void check_epilogue_coeffs(const char* op, const at::Tensor& scale,
+                           const at::Tensor& shift, int64_t K) {
+    check_flat(op, "scale", scale, at::kFloat, K);
+    check_flat(op, "shift", shift, at::kFloat, K);
+    check_aligned16(op, "scale", scale);
+    check_aligned16(op, "shift", shift);
+}
+
+// What a conv launch takes besides its two operands; undefined = absent.
+// accum: added to the output before the round (dgrad). scale/shift
+// (+ residual, relu): the inference epilogue (forward, stem).
+struct ConvExtras {
+    at::Tensor accum, scale, shift, residual;
+    bool relu = false;
+};
+
+// The launch sequence of the fwd / dgrad kernels: plan -> split-K partials
+// -> launch -> combine. Operands are checked by the caller except for their
+// device. Returns the output and, with want_stats (forward), the BN partials
+// [plan.stats_rows][2][K] that feed bn_fwd_finalize_launch.
+std::tuple<at::Tensor, at::Tensor> conv_run(
+    const char* op, fda::ConvMode mode, const at::Tensor& src,
+    const at::Tensor& wgt, const fda::ConvGeom& g, bool want_stats,
+    const ConvExtras& ex) {
+    TORCH_CHECK(!ex.scale.defined() || (!want_stats && !ex.accum.defined()),
+                op, ": the inference epilogue excludes stats and accum");
+    const fda::ConvPlan plan = fda::conv_igemm_plan(g, mode);
+    const long M = g.rows(mode);
+    const int OC = g.oc(mode);
+    TORCH_CHECK(plan.sk == 1 || OC <= 2048, op,
+                ": split-K shapes need at most 2048 output channels");
+    check_device(op, {src, wgt, ex.accum, ex.scale, ex.shift, ex.residual});
+    const auto cl = src.options().memory_format(at::MemoryFormat::ChannelsLast);
+    const auto f32 = src.options().dtype(at::kFloat);
+    auto out = mode == fda::CONV_DGRAD ? at::empty({g.N, g.C, g.H, g.W}, cl)
+                                       : at::empty({g.N, g.K, g.P, g.Q}, cl);
+    at::Tensor part, skp;
+    if (want_stats) part = at::empty({plan.stats_rows, 2, OC}, f32);
+    float* stats = want_stats ? part.data_ptr<float>() : nullptr;
+    const void* accsrc = ex.accum.defined() ? ex.accum.data_ptr() : nullptr;
+    const fda::EpiInfer epi{
+        ex.scale.defined() ? ex.scale.data_ptr<float>() : nullptr,
+        ex.scale.defined() ? ex.shift.data_ptr<float>() : nullptr,
+        ex.residual.defined()
+            ? (const unsigned short*)ex.residual.data_ptr() : nullptr,
+        ex.relu};
+    const fda::EpiInfer* epip = ex.scale.defined() ? &epi : nullptr;
+    if (plan.sk == 1) {
+        fda::conv_igemm_launch(src.data_ptr(), wgt.data_ptr(), out.data_ptr(),
+                               g, mode, plan, cur_stream(), stats, nullptr,
+                               accsrc, epip);
+        return {out, part};
     }
-    if (want_stats) part = at::empty({(M + BM - 1) / BM, 2, K}, f32);
-    fda::conv_igemm_launch(x.data_ptr(), w.data_ptr(), y.data_ptr(),
-                           N, H, W, C, K, P, Q, R, S, (int)sy, (int)sx,
-                           (int)py, (int)px, /*dgrad=*/false, cur_stream(),
-                           want_stats ? part.data_ptr<float>() : nullptr);
-    return {y, part};
+    // fp32 partials; the combine kernel rounds and takes over the stats,
+    // the accum and the epilogue
+    skp = at::empty({(long)plan.sk * M * OC}, f32);
+    fda::conv_igemm_launch(src.data_ptr(), wgt.data_ptr(), out.data_ptr(), g,
+                           mode, plan, cur_stream(), nullptr,
+                           skp.data_ptr<float>());
+    fda::conv_skcombine_launch(skp.data_ptr<float>(), out.data_ptr(), stats, M,
+                               OC, plan.sk, cur_stream(), accsrc, epip);
+    return {out, part};
+}
+
+// x [N,C,H,W], w [K,C,R,S], both channels_last bf16
+fda::ConvGeom check_fwd(const char* op, const at::Tensor& x,
+                        const at::Tensor& w, int64_t sy, int64_t sx,
+                        int64_t py, int64_t px) {
+    check_cl_bf16(op, "x", x);
+    check_cl_bf16(op, "w", w);
+    const auto g = conv_geometry(op, x.size(0), x.size(1), x.size(2),
+                                 x.size(3), w.size(0), w.size(2), w.size(3),
+                                 sy, sx, py, px);
+    TORCH_CHECK(w.size(1) == x.size(1), op, ": channel mismatch");
+    return g;
 }
 
 at::Tensor conv_igemm_fwd(at::Tensor x, at::Tensor w,
                           int64_t sy, int64_t sx, int64_t py, int64_t px) {
-    return std::get<0>(conv_igemm_fwd_impl(x, w, sy, sx, py, px, false));
+    const char* op = "conv_igemm_fwd";
+    const auto g = check_fwd(op, x, w, sy, sx, py, px);
+    return std::get<0>(conv_run(op, fda::CONV_FWD, x, w, g, false, {}));
 }
 
+// forward with per-m-tile BN partials (sum/sumsq of the rounded output)
 std::tuple<at::Tensor, at::Tensor> conv_igemm_fwd_stats(
     at::Tensor x, at::Tensor w, int64_t sy, int64_t sx, int64_t py,
     int64_t px) {
-    return conv_igemm_fwd_impl(x, w, sy, sx, py, px, true);
+    const char* op = "conv_igemm_fwd_stats";
+    const auto g = check_fwd(op, x, w, sy, sx, py, px);
+    return conv_run(op, fda::CONV_FWD, x, w, g, true, {});
 }
 
+// dy: [N,K,P,Q] channels_last; wt: [R*S*C, K] row-major (pre-transposed
+// weight, k contiguous). Output dx: [N,C,H,W] channels_last.
+// accum: optional bf16 tensor in dx's layout added into the result in the
+// epilogue (residual-junction grad fusion, ops/conv.py).
 at::Tensor conv_igemm_dgrad(at::Tensor dy, at::Tensor wt,
                             int64_t C, int64_t H, int64_t W,
                             int64_t R, int64_t S,
                             int64_t sy, int64_t sx, int64_t py, int64_t px,
                             c10::optional<at::Tensor> accum) {
-    // accum: optional bf16 tensor in dx's layout added into the result in
-    // the epilogue (residual-junction grad fusion, ops/conv.py).
-    // dy: [N,K,P,Q] channels_last; wt: [R*S*C, K] row-major (pre-transposed
-    // weight, k contiguous). Output dx: [N,C,H,W] channels_last.
-    TORCH_CHECK(dy.dim() == 4 && wt.dim() == 2);
-    const int N = (int)dy.size(0), K = (int)dy.size(1), P = (int)dy.size(2),
-              Q = (int)dy.size(3);
-    check_conv_operands(dy, wt, C, K);
-    TORCH_CHECK(wt.size(0) == R * S * C && wt.size(1) == K, "wt shape mismatch");
-    auto dx = at::empty({N, C, H, W},
-                        dy.options().memory_format(at::MemoryFormat::ChannelsLast));
-    const void* accp = nullptr;
+    const char* op = "conv_igemm_dgrad";
+    check_cl_bf16(op, "dy", dy);
+    const auto g = conv_geometry(op, dy.size(0), C, H, W, dy.size(1), R, S,
+                                 sy, sx, py, px);
+    check_dy(op, dy, g);
+    TORCH_CHECK(wt.dim() == 2 && wt.scalar_type() == at::kBFloat16 &&
+                    wt.is_contiguous() && wt.size(0) == R * S * C &&
+                    wt.size(1) == g.K,
+                op, ": wt must be contiguous bf16 [R*S*C][K]");
+    ConvExtras ex;
     if (accum.has_value() && accum->defined()) {
-        TORCH_CHECK(accum->is_cuda() &&
-                    accum->is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                    accum->scalar_type() == at::kBFloat16 &&
-                    accum->numel() == dx.numel(),
-                    "dgrad accum tensor must be channels_last bf16 of dx's shape");
-        accp = accum->data_ptr();
+        ex.accum = *accum;
+        TORCH_CHECK(ex.accum.scalar_type() == at::kBFloat16 &&
+                        ex.accum.sizes() == at::IntArrayRef({g.N, C, H, W}) &&
+                        ex.accum.is_contiguous(at::MemoryFormat::ChannelsLast),
+                    op, ": accum must be channels_last bf16 of dx's shape [",
+                    g.N, ",", C, ",", H, ",", W, "]");
+        check_aligned16(op, "accum", ex.accum);
     }
-    const long M = (long)N * H * W;
-    int BM, BN, SK = 1;
-    if (sy == 1 && sx == 1)                 // parity classes already fan out
-        fda::conv_igemm_plan(M, (int)C, (long)R * S * (K / 64), 1,
-                             &BM, &BN, &SK);
-    if (SK > 1) {
-        auto skp = at::empty({(long)SK * M * C},
-                             dy.options().dtype(at::kFloat));
-        fda::conv_igemm_launch(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(),
-                               N, (int)H, (int)W, (int)C, K, P, Q, (int)R,
-                               (int)S, (int)sy, (int)sx, (int)py, (int)px,
-                               /*dgrad=*/true, cur_stream(), nullptr,
-                               skp.data_ptr<float>(), SK);
-        fda::conv_skcombine_launch(skp.data_ptr<float>(), dx.data_ptr(),
-                                   nullptr, M, (int)C, SK,
-                                   fda::conv_skcombine_blocks(M, (int)C),
-                                   cur_stream(), accp);
-        return dx;
-    }
-    fda::conv_igemm_launch(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(),
-                           N, (int)H, (int)W, (int)C, K, P, Q, (int)R, (int)S,
-                           (int)sy, (int)sx, (int)py, (int)px, /*dgrad=*/true,
-                           cur_stream(), nullptr, nullptr, 1, accp);
-    return dx;
+    return std::get<0>(conv_run(op, fda::CONV_DGRAD, dy, wt, g, false, ex));
+}
+
+// dy: [N,K,P,Q] channels_last bf16; x: [N,C,H,W] channels_last bf16
+fda::ConvGeom check_wgrad(const char* op, const at::Tensor& dy,
+                          const at::Tensor& x, int64_t R, int64_t S,
+                          int64_t sy, int64_t sx, int64_t py, int64_t px) {
+    check_cl_bf16(op, "dy", dy);
+    check_cl_bf16(op, "x", x);
+    const auto g = conv_geometry(op, x.size(0), x.size(1), x.size(2),
+                                 x.size(3), dy.size(1), R, S, sy, sx, py, px);
+    TORCH_CHECK(dy.size(0) == x.size(0), op, ": batch size mismatch: dy has ",
+                dy.size(0), ", x has ", x.size(0));
+    check_dy(op, dy, g);
+    return g;
 }
 
 // wgrad: ws [K][R*S*C] fp32 (the channels_last weight-grad layout
-// [K][R][S][C] flattened), PRE-ZEROED, accumulated in place.
-// dy: [N,K,P,Q] channels_last bf16; x: [N,C,H,W] channels_last bf16.
+// [K][R][S][C] flattened), PRE-ZEROED, accumulated in place. ws is typically
+// a slice of the step-scoped wgrad arena (ops/conv.py), which saves the
+// per-layer zeros launch.
 void conv_igemm_wgrad_into(at::Tensor dy, at::Tensor x, at::Tensor ws,
                            int64_t R, int64_t S,
                            int64_t sy, int64_t sx, int64_t py, int64_t px) {
-    // ws is typically a slice of the step-scoped wgrad arena (ops/conv.py),
-    // which saves the per-layer zeros launch.
-    TORCH_CHECK(dy.dim() == 4 && x.dim() == 4);
-    const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2),
-              W = (int)x.size(3);
-    const int K = (int)dy.size(1), P = (int)dy.size(2), Q = (int)dy.size(3);
-    check_conv_operands(dy, x, C, K);
-    TORCH_CHECK(ws.is_cuda() && ws.scalar_type() == at::kFloat &&
-                ws.is_contiguous());
-    TORCH_CHECK(ws.numel() == (int64_t)K * R * S * C);
+    const char* op = "conv_igemm_wgrad_into";
+    const auto g = check_wgrad(op, dy, x, R, S, sy, sx, py, px);
+    check_flat(op, "ws", ws, at::kFloat, (int64_t)g.K * R * S * g.C);
+    check_device(op, {dy, x, ws});
     fda::conv_wgrad_launch(dy.data_ptr(), x.data_ptr(), ws.data_ptr<float>(),
-                           N, H, W, C, K, P, Q, (int)R, (int)S, (int)sy,
-                           (int)sx, (int)py, (int)px, cur_stream());
+                           g, cur_stream());
 }
 
 at::Tensor conv_igemm_wgrad(at::Tensor dy, at::Tensor x,
                             int64_t R, int64_t S,
                             int64_t sy, int64_t sx, int64_t py, int64_t px) {
-    TORCH_CHECK(dy.dim() == 4 && x.dim() == 4);
+    TORCH_CHECK(dy.dim() == 4 && x.dim() == 4,
+                "conv_igemm_wgrad: dy and x must be 4-D");
     auto ws = at::zeros({dy.size(1), R * S * x.size(1)},
                         x.options().dtype(at::kFloat));
     conv_igemm_wgrad_into(dy, x, ws, R, S, sy, sx, py, px);
     return ws;
 }
 
-
-// Operand checks shared by the stem entry points. x8: [N,8,Hp,Wp]
-// channels_last bf16 (spatially pre-padded, channels 3..7 zero). Output
-// pixel (p, q) reads filter row r from input row p*sy + r, columns
-// q*sx .. q*sx + 7, which must stay inside the padded image.
-static void check_stem_geometry(const char* op, const at::Tensor& x8,
-                                int64_t K, int64_t R, int64_t sy, int64_t sx,
-                                int64_t P, int64_t Q) {
+// Operand checks shared by the stem entry points, and their geometry. x8:
+// [N,8,Hp,Wp] channels_last bf16 (spatially pre-padded, channels 3..7
+// zero). Output pixel (p, q) reads filter row r from input row p*sy + r,
+// columns q*sx .. q*sx + 7, which must stay inside the padded image.
+fda::ConvGeom check_stem_geometry(const char* op, const at::Tensor& x8,
+                                  int64_t K, int64_t R, int64_t sy, int64_t sx,
+                                  int64_t P, int64_t Q) {
     TORCH_CHECK(x8.scalar_type() == at::kBFloat16 && x8.dim() == 4 &&
                     x8.is_contiguous(at::MemoryFormat::ChannelsLast) &&
                     x8.size(1) == 8,
@@ -736,145 +774,103 @@ static void check_stem_geometry(const char* op, const at::Tensor& x8,
                     (Q - 1) * sx + 8 <= x8.size(3),
                 op, ": output ", P, "x", Q, " reads outside the padded ",
                 x8.size(2), "x", x8.size(3), " input");
+    fda::ConvGeom g{};
+    g.N = (int)x8.size(0); g.H = (int)x8.size(2); g.W = (int)x8.size(3);
+    g.C = 8; g.K = (int)K; g.P = (int)P; g.Q = (int)Q; g.R = (int)R; g.S = 1;
+    g.sy = (int)sy; g.sx = (int)sx;
+    return g;
 }
 
-// wpad: [K][R][64] bf16 (s==7 and c>=3 taps zero). With want_stats also the
-// per-m-tile BN partials [tiles][2][K]; undefined otherwise.
-static std::tuple<at::Tensor, at::Tensor> conv_stem_fwd_impl(
-    const at::Tensor& x8, const at::Tensor& wpad, int64_t R, int64_t sy,
-    int64_t sx, int64_t P, int64_t Q, bool want_stats) {
-    const char* op = "conv_stem_fwd";
+// The stem forward. wpad: [K][R][64] bf16 (s==7 and c>=3 taps zero). With
+// want_stats also the per-m-tile BN partials [tiles][2][K]; with ex.scale
+// the inference epilogue.
+std::tuple<at::Tensor, at::Tensor> conv_stem_run(
+    const char* op, const at::Tensor& x8, const at::Tensor& wpad, int64_t R,
+    int64_t sy, int64_t sx, int64_t P, int64_t Q, bool want_stats,
+    const ConvExtras& ex) {
     TORCH_CHECK(wpad.dim() == 3 && wpad.is_contiguous() &&
                     wpad.scalar_type() == at::kBFloat16 &&
                     wpad.size(1) == R && wpad.size(2) == 64,
                 op, ": wpad must be contiguous bf16 [K][R][64]");
-    const int K = (int)wpad.size(0);
-    check_stem_geometry(op, x8, K, R, sy, sx, P, Q);
-    check_device(op, {x8, wpad});
-    const int N = (int)x8.size(0), Hp = (int)x8.size(2), Wp = (int)x8.size(3);
-    auto y = at::empty({N, K, P, Q},
+    const auto g = check_stem_geometry(op, x8, wpad.size(0), R, sy, sx, P, Q);
+    if (ex.scale.defined()) check_epilogue_coeffs(op, ex.scale, ex.shift, g.K);
+    check_device(op, {x8, wpad, ex.scale, ex.shift});
+    auto y = at::empty({g.N, g.K, g.P, g.Q},
                        x8.options().memory_format(at::MemoryFormat::ChannelsLast));
     at::Tensor part;
-    if (want_stats) {
-        const long M = (long)N * P * Q;
-        part = at::empty({(M + 256 - 1) / 256, 2, K},
-                         x8.options().dtype(at::kFloat));
-    }
-    fda::conv_stem_fwd_launch(x8.data_ptr(), wpad.data_ptr(), y.data_ptr(),
-                              N, Hp, Wp, K, (int)P, (int)Q, (int)R, (int)sy,
-                              (int)sx, cur_stream(),
-                              want_stats ? part.data_ptr<float>() : nullptr);
+    if (want_stats)
+        part = at::empty(
+            {fda::conv_igemm_plan(g, fda::CONV_STEM).stats_rows, 2, g.K},
+            x8.options().dtype(at::kFloat));
+    const fda::EpiInfer epi{
+        ex.scale.defined() ? ex.scale.data_ptr<float>() : nullptr,
+        ex.scale.defined() ? ex.shift.data_ptr<float>() : nullptr, nullptr,
+        ex.relu};
+    fda::conv_stem_fwd_launch(x8.data_ptr(), wpad.data_ptr(), y.data_ptr(), g,
+                              cur_stream(),
+                              want_stats ? part.data_ptr<float>() : nullptr,
+                              ex.scale.defined() ? &epi : nullptr);
     return {y, part};
 }
 
 at::Tensor conv_stem_fwd(at::Tensor x8, at::Tensor wpad, int64_t R,
                          int64_t sy, int64_t sx, int64_t P, int64_t Q) {
-    return std::get<0>(conv_stem_fwd_impl(x8, wpad, R, sy, sx, P, Q, false));
+    return std::get<0>(conv_stem_run("conv_stem_fwd", x8, wpad, R, sy, sx, P,
+                                     Q, false, {}));
 }
 
 std::tuple<at::Tensor, at::Tensor> conv_stem_fwd_stats(
     at::Tensor x8, at::Tensor wpad, int64_t R, int64_t sy, int64_t sx,
     int64_t P, int64_t Q) {
-    return conv_stem_fwd_impl(x8, wpad, R, sy, sx, P, Q, true);
+    return conv_stem_run("conv_stem_fwd_stats", x8, wpad, R, sy, sx, P, Q,
+                         true, {});
 }
 
-// The config a forward conv of this geometry runs: (BM, BN, SK, ring), from
-// the functions the launcher itself obeys. For tests that must know which
-// kernel a shape reaches.
+// The config a forward conv with M output rows runs: (BM, BN, SK, ring),
+// from the plan the launcher itself obeys. For tests that must know which
+// kernel a shape reaches. M beyond int range is refused as bad geometry: no
+// conv entry point accepts such a shape.
 std::tuple<int64_t, int64_t, int64_t, bool> conv_igemm_fwd_config(
     int64_t M, int64_t C, int64_t K, int64_t R, int64_t S) {
-    TORCH_CHECK(M >= 1 && C >= 64 && C % 64 == 0 && K >= 64 && K % 64 == 0 &&
-                    R >= 1 && S >= 1,
+    TORCH_CHECK(M >= 1 && M <= INT32_MAX && C >= 64 && C % 64 == 0 &&
+                    K >= 64 && K % 64 == 0 && R >= 1 && S >= 1,
                 "conv_igemm_fwd_config: bad geometry");
-    int BM, BN, SK;
-    fda::conv_igemm_plan((long)M, (int)K, (long)R * S * (C / 64), 1, &BM, &BN,
-                         &SK);
-    const long blocks = ((M + BM - 1) / BM) * (K / BN) * SK;
-    return {BM, BN, SK, fda::conv_igemm_ring(blocks, BN)};
+    fda::ConvGeom g{};
+    g.N = 1; g.P = 1; g.Q = (int)M;      // the plan sees M = N*P*Q only
+    g.C = (int)C; g.K = (int)K; g.R = (int)R; g.S = (int)S;
+    const auto plan = fda::conv_igemm_plan(g, fda::CONV_FWD);
+    return {plan.bm, plan.bn, plan.sk, plan.ring};
 }
 
 // ---- inference forward: conv + eval BN + residual + ReLU in one kernel ----
-// Shape, dtype and layout checks come first and check_device last, so every
-// refusal can be exercised on a machine without a GPU.
-
-// scale/shift of the inference epilogue: K floats each
-static void check_epilogue_coeffs(const char* op, const at::Tensor& scale,
-                                  const at::Tensor& shift, int64_t K) {
-    check_flat(op, "scale", scale, at::kFloat, K);
-    check_flat(op, "shift", shift, at::kFloat, K);
-    // the kernels read them as 16-B vectors
-    TORCH_CHECK((reinterpret_cast<uintptr_t>(scale.data_ptr()) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(shift.data_ptr()) & 15) == 0,
-                op, ": scale and shift must be 16-byte aligned");
-}
 
 // y = bf16(relu(scale[k] * conv(x, w) + shift[k] + residual)), rounded once
 // from the fp32 accumulator. residual: an empty tensor for none, else bf16
 // channels_last of exactly the output's shape. The output is allocated
-// here, so no operand can alias it.
+// in conv_run, so no operand can alias it. Split-K shapes run the plain
+// forward into fp32 partials and the combine kernel applies the epilogue.
 at::Tensor conv_igemm_fwd_fused(at::Tensor x, at::Tensor w, at::Tensor scale,
                                 at::Tensor shift, at::Tensor residual,
                                 bool relu, int64_t sy, int64_t sx, int64_t py,
                                 int64_t px) {
     const char* op = "conv_igemm_fwd_fused";
-    TORCH_CHECK(x.dim() == 4 && w.dim() == 4 &&
-                    x.scalar_type() == at::kBFloat16 &&
-                    w.scalar_type() == at::kBFloat16 &&
-                    x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                    w.is_contiguous(at::MemoryFormat::ChannelsLast),
-                op, ": x and w must be 4-D channels_last bf16");
-    const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2),
-              W = (int)x.size(3);
-    const int K = (int)w.size(0), R = (int)w.size(2), S = (int)w.size(3);
-    TORCH_CHECK(C % 64 == 0 && K % 64 == 0 && C >= 64 && K >= 64, op,
-                ": C and K must be multiples of 64");
-    TORCH_CHECK((int)w.size(1) == C, op, ": channel mismatch");
-    TORCH_CHECK(N >= 1 && sy >= 1 && sx >= 1 && py >= 0 && px >= 0 &&
-                    H + 2 * py >= R && W + 2 * px >= S,
-                op, ": bad stride/padding or filter larger than the input");
-    const int P = (H + 2 * (int)py - R) / (int)sy + 1;
-    const int Q = (W + 2 * (int)px - S) / (int)sx + 1;
-    check_epilogue_coeffs(op, scale, shift, K);
-    const bool has_res = residual.defined() && residual.numel() > 0;
-    if (has_res)
+    const auto g = check_fwd(op, x, w, sy, sx, py, px);
+    check_epilogue_coeffs(op, scale, shift, g.K);
+    ConvExtras ex;
+    ex.scale = scale;
+    ex.shift = shift;
+    ex.relu = relu;
+    if (residual.defined() && residual.numel() > 0) {
         TORCH_CHECK(residual.scalar_type() == at::kBFloat16 &&
-                        residual.dim() == 4 && residual.size(0) == N &&
-                        residual.size(1) == K && residual.size(2) == P &&
-                        residual.size(3) == Q &&
+                        residual.sizes() ==
+                            at::IntArrayRef({g.N, g.K, g.P, g.Q}) &&
                         residual.is_contiguous(at::MemoryFormat::ChannelsLast),
                     op, ": residual must be channels_last bf16 of the "
-                    "output's shape [", N, ",", K, ",", P, ",", Q, "]");
-    if (has_res)
-        TORCH_CHECK((reinterpret_cast<uintptr_t>(residual.data_ptr()) & 15) == 0,
-                    op, ": residual must be 16-byte aligned");
-    const long M = (long)N * P * Q;
-    int BM, BN, SK;
-    fda::conv_igemm_plan(M, K, (long)R * S * (C / 64), 1, &BM, &BN, &SK);
-    if (SK > 1)
-        TORCH_CHECK(K <= 2048, op, ": split-K shapes need K <= 2048");
-    check_device(op, {x, w, scale, shift, has_res ? residual : at::Tensor()});
-    auto y = at::empty({N, K, P, Q},
-                       x.options().memory_format(at::MemoryFormat::ChannelsLast));
-    const void* resp = has_res ? residual.data_ptr() : nullptr;
-    if (SK > 1) {
-        // fp32 partials from the plain forward; the combine kernel applies
-        // the epilogue, so these shapes stay fused as well
-        auto skp = at::empty({(long)SK * M * K}, x.options().dtype(at::kFloat));
-        fda::conv_igemm_launch(x.data_ptr(), w.data_ptr(), y.data_ptr(), N, H,
-                               W, C, K, P, Q, R, S, (int)sy, (int)sx, (int)py,
-                               (int)px, /*dgrad=*/false, cur_stream(), nullptr,
-                               skp.data_ptr<float>(), SK);
-        fda::conv_skcombine_fused_launch(
-            skp.data_ptr<float>(), y.data_ptr(), M, K, SK,
-            fda::conv_skcombine_blocks(M, K), scale.data_ptr<float>(),
-            shift.data_ptr<float>(), resp, relu, cur_stream());
-        return y;
+                    "output's shape [", g.N, ",", g.K, ",", g.P, ",", g.Q, "]");
+        check_aligned16(op, "residual", residual);
+        ex.residual = residual;
     }
-    fda::conv_igemm_fwd_fused_launch(
-        x.data_ptr(), w.data_ptr(), y.data_ptr(), N, H, W, C, K, P, Q, R, S,
-        (int)sy, (int)sx, (int)py, (int)px, scale.data_ptr<float>(),
-        shift.data_ptr<float>(), resp, relu, cur_stream());
-    return y;
+    return std::get<0>(conv_run(op, fda::CONV_FWD, x, w, g, false, ex));
 }
 
 // stem conv + eval BN (+ ReLU); operands as conv_stem_fwd
@@ -882,23 +878,12 @@ at::Tensor conv_stem_fwd_fused(at::Tensor x8, at::Tensor wpad,
                                at::Tensor scale, at::Tensor shift, bool relu,
                                int64_t R, int64_t sy, int64_t sx, int64_t P,
                                int64_t Q) {
-    const char* op = "conv_stem_fwd_fused";
-    TORCH_CHECK(wpad.dim() == 3 && wpad.is_contiguous() &&
-                    wpad.scalar_type() == at::kBFloat16 &&
-                    wpad.size(1) == R && wpad.size(2) == 64,
-                op, ": wpad must be contiguous bf16 [K][R][64]");
-    const int K = (int)wpad.size(0);
-    check_stem_geometry(op, x8, K, R, sy, sx, P, Q);
-    check_epilogue_coeffs(op, scale, shift, K);
-    check_device(op, {x8, wpad, scale, shift});
-    const int N = (int)x8.size(0), Hp = (int)x8.size(2), Wp = (int)x8.size(3);
-    auto y = at::empty({N, K, P, Q},
-                       x8.options().memory_format(at::MemoryFormat::ChannelsLast));
-    fda::conv_stem_fwd_fused_launch(
-        x8.data_ptr(), wpad.data_ptr(), y.data_ptr(), N, Hp, Wp, K, (int)P,
-        (int)Q, (int)R, (int)sy, (int)sx, scale.data_ptr<float>(),
-        shift.data_ptr<float>(), relu, cur_stream());
-    return y;
+    ConvExtras ex;
+    ex.scale = scale;
+    ex.shift = shift;
+    ex.relu = relu;
+    return std::get<0>(conv_stem_run("conv_stem_fwd_fused", x8, wpad, R, sy,
+                                     sx, P, Q, false, ex));
 }
 
 // One launch folds the eval-mode BN of every layer into the fp32 arena:
@@ -941,15 +926,13 @@ at::Tensor conv_stem_wgrad(at::Tensor dy, at::Tensor x8, int64_t R,
     TORCH_CHECK(dy.scalar_type() == at::kBFloat16 && dy.dim() == 4 &&
                     dy.is_contiguous(at::MemoryFormat::ChannelsLast),
                 op, ": dy must be 4-D channels_last bf16");
-    const int K = (int)dy.size(1), P = (int)dy.size(2), Q = (int)dy.size(3);
-    check_stem_geometry(op, x8, K, R, sy, sx, P, Q);
+    const auto g = check_stem_geometry(op, x8, dy.size(1), R, sy, sx,
+                                       dy.size(2), dy.size(3));
     TORCH_CHECK(dy.size(0) == x8.size(0), op, ": batch size mismatch");
     check_device(op, {dy, x8});
-    const int N = (int)x8.size(0), Hp = (int)x8.size(2), Wp = (int)x8.size(3);
-    auto ws = at::zeros({K, R * 64}, x8.options().dtype(at::kFloat));
+    auto ws = at::zeros({g.K, R * 64}, x8.options().dtype(at::kFloat));
     fda::conv_stem_wgrad_launch(dy.data_ptr(), x8.data_ptr(),
-                                ws.data_ptr<float>(), N, Hp, Wp, K, P, Q,
-                                (int)R, (int)sy, (int)sx, cur_stream());
+                                ws.data_ptr<float>(), g, cur_stream());
     return ws;   // [K][R*64]; host slices [K][R][s<7][c<3]
 }
 
@@ -1122,6 +1105,8 @@ at::Tensor preprocess_batch(at::Tensor arena, at::Tensor meta, int64_t crop,
                                  bf16 ? DT::BF16 : DT::F32, stream);
     return out;
 }
+
+}  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("preprocess_batch", &preprocess_batch, pybind11::arg("arena"),

@@ -29,7 +29,9 @@
 //   OC % 128 != 0 : BM=256 x BN=64,  4 waves as 4x1, LDS 2x40 KiB
 // Each tile has a second config for grids big enough to fill it: BK=32
 // K-steps on a 3-buffer counted ring (3x16 KiB at 3 blocks/CU, 3x20 KiB at
-// 2), chosen in conv_dispatch. Kernels in this file: conv_igemm_kernel
+// 2). Tile, ring and split-K are decided in one place, conv_igemm_plan
+// (a ConvPlan from a ConvGeom and a mode): conv_dispatch obeys it and the
+// bindings size their workspaces from it. Kernels in this file: conv_igemm_kernel
 // fwd+dgrad x 2 tiles x {BK64 2-buf, BK32 3-ring} (8) + the stem (1), the
 // four fwd configs and the stem once more with the inference epilogue
 // (EpiInfer: eval BN + residual + ReLU before the single bf16 round),
@@ -63,8 +65,10 @@
 // else (grouped/dilated convs) falls back to the library path.
 
 #include <hip/hip_runtime.h>
+#include <cassert>
 #include <cstdlib>
 #include "fda_common.h"
+#include "fda_kernels.h"
 
 namespace fda {
 
@@ -78,7 +82,6 @@ __device__ __align__(16) static const unsigned short conv_zero16[8] = {0};
         (const __attribute__((address_space(1))) void*)(gptr),              \
         (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
 
-enum ConvMode { CONV_FWD = 0, CONV_DGRAD = 1, CONV_STEM = 2 };
 // CONV_STEM: small-C stem conv on a channel-padded (C=8) pre-padded input.
 // Taps are r-only: each K-step covers one filter row r as 64 virtual
 // channels = 8 pixels (s=0..7, s==7 zero-padded in wpad) x 8 channels
@@ -86,17 +89,10 @@ enum ConvMode { CONV_FWD = 0, CONV_DGRAD = 1, CONV_STEM = 2 };
 
 constexpr int BK = 64;
 
-// Inference epilogue (eval BatchNorm + residual + ReLU on the fp32
-// accumulator, one bf16 round). Passed to conv_igemm_kernel /
-// conv_skcombine_kernel as the optional trailing EPI argument; the
-// training instantiations pass none, so their code and argument lists
-// are those of a kernel without it.
-struct EpiInfer {
-    const float* scale;                  // [OC]
-    const float* shift;                  // [OC]
-    const unsigned short* residual;      // output's layout, or null
-    int relu;
-};
+// The inference epilogue (EpiInfer, fda_kernels.h) is passed to
+// conv_igemm_kernel / conv_skcombine_kernel as the optional trailing EPI
+// argument; the training instantiations pass none, so their code and
+// argument lists are those of a kernel without it.
 template <class E>
 __device__ __forceinline__ const E& epi_of(const E& e) { return e; }
 
@@ -591,19 +587,13 @@ void conv_igemm_kernel(
 template <int MODE, int BM, int BN, int WN, int NBUF = 2, int BKT = BK,
           class... EPI>
 static void launch_cfg(const void* src, const void* wgt, void* out,
-                       int N, int H, int W, int C, int K, int P, int Q,
-                       int R, int S, int sy, int sx, int py, int px,
-                       hipStream_t stream, float* stats = nullptr,
-                       float* skpart = nullptr, int SK = 1,
-                       const void* accsrc = nullptr, EPI... epi) {
-    const int OC = (MODE == CONV_DGRAD) ? C : K;
-    const long M = (MODE != CONV_DGRAD)
-        ? (long)N * P * Q
-        : (long)N * ((H + sy - 1) / sy) * ((W + sx - 1) / sx);
-    const unsigned zbase = (MODE != CONV_DGRAD) ? 1u : (unsigned)(sy * sx);
+                       const ConvGeom& g, int SK, hipStream_t stream,
+                       float* stats, float* skpart, const void* accsrc,
+                       EPI... epi) {
+    constexpr ConvMode mode = (ConvMode)MODE;
     constexpr unsigned NTHREADS = (BM / 64) * (BN / 64) * 64;
-    dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)(OC / BN),
-              zbase * (unsigned)SK);
+    dim3 grid((unsigned)((g.rows(mode) + BM - 1) / BM),
+              (unsigned)(g.oc(mode) / BN), (unsigned)(g.classes(mode) * SK));
     const size_t shmem = NBUF * (BM * BKT + BN * BKT) * sizeof(unsigned short);
     if (shmem > 65536) {
         static bool raised = [] {
@@ -619,8 +609,9 @@ static void launch_cfg(const void* src, const void* wgt, void* out,
                        grid, dim3(NTHREADS), shmem, stream,
                        (const unsigned short*)src,
                        (const unsigned short*)wgt, (unsigned short*)out,
-                       N, H, W, C, K, P, Q, R, S, sy, sx, py, px, stats,
-                       skpart, SK, (const unsigned short*)accsrc, epi...);
+                       g.N, g.H, g.W, g.C, g.K, g.P, g.Q, g.R, g.S, g.sy,
+                       g.sx, g.py, g.px, stats, skpart, SK,
+                       (const unsigned short*)accsrc, epi...);
 }
 
 // ---- split-K combine: y = bf16(sum_sk part) (+ BN stats partials) --------
@@ -721,56 +712,43 @@ __global__ __launch_bounds__(256) void conv_skcombine_kernel(
     }
 }
 
-int conv_skcombine_blocks(long M, int OC) {
-    const int rpb = 256 / (OC / 8);
+static int conv_skcombine_blocks(long M, int OC) {
+    // OC > 2048 has no combine kernel; the bindings refuse such a plan
+    const int rpb = OC <= 2048 ? 256 / (OC / 8) : 1;
     long b = (M + rpb - 1) / rpb;
     return (int)(b < 512 ? b : 512);
 }
 
 void conv_skcombine_launch(const float* part, void* y, float* stats, long M,
-                           int OC, int SK, int nblocks, hipStream_t stream,
-                           const void* accsrc) {
-    hipLaunchKernelGGL(conv_skcombine_kernel<>, dim3(nblocks), dim3(256), 0,
-                       stream, part, (unsigned short*)y, stats, M, OC, SK,
-                       (const unsigned short*)accsrc);
-}
-
-void conv_skcombine_fused_launch(const float* part, void* y, long M, int OC,
-                                 int SK, int nblocks, const float* scale,
-                                 const float* shift, const void* residual,
-                                 bool relu, hipStream_t stream) {
-    const EpiInfer epi{scale, shift, (const unsigned short*)residual, relu};
-    hipLaunchKernelGGL(conv_skcombine_kernel<EpiInfer>, dim3(nblocks),
-                       dim3(256), 0, stream, part, (unsigned short*)y,
-                       (float*)nullptr, M, OC, SK,
-                       (const unsigned short*)nullptr, epi);
+                           int OC, int SK, hipStream_t stream,
+                           const void* accsrc, const EpiInfer* epi) {
+    assert(epi == nullptr || (stats == nullptr && accsrc == nullptr));
+    const dim3 grid(conv_skcombine_blocks(M, OC));
+    if (epi != nullptr)
+        hipLaunchKernelGGL(conv_skcombine_kernel<EpiInfer>, grid, dim3(256),
+                           0, stream, part, (unsigned short*)y,
+                           (float*)nullptr, M, OC, SK,
+                           (const unsigned short*)nullptr, *epi);
+    else
+        hipLaunchKernelGGL(conv_skcombine_kernel<>, grid, dim3(256), 0,
+                           stream, part, (unsigned short*)y, stats, M, OC, SK,
+                           (const unsigned short*)accsrc);
 }
 
 void conv_stem_fwd_launch(const void* src, const void* wgt, void* out,
-                          int N, int Hp, int Wp, int K, int P, int Q,
-                          int R, int sy, int sx, hipStream_t stream,
-                          float* stats) {
-    // src: channel-padded (C=8) spatially pre-padded input [N,Hp,Wp,8];
-    // wgt: wpad [K][R][64]; out: [N*P*Q][K]
-    launch_cfg<CONV_STEM, 256, 64, 1>(src, wgt, out, N, Hp, Wp, /*C=*/8, K,
-                                      P, Q, R, /*S=*/1, sy, sx, 0, 0, stream,
-                                      stats);
-}
-
-void conv_stem_fwd_fused_launch(const void* src, const void* wgt, void* out,
-                                int N, int Hp, int Wp, int K, int P, int Q,
-                                int R, int sy, int sx, const float* scale,
-                                const float* shift, bool relu,
-                                hipStream_t stream) {
-    const EpiInfer epi{scale, shift, nullptr, relu};
-    launch_cfg<CONV_STEM, 256, 64, 1, 2, BK, EpiInfer>(
-        src, wgt, out, N, Hp, Wp, /*C=*/8, K, P, Q, R, /*S=*/1, sy, sx, 0, 0,
-        stream, nullptr, nullptr, 1, nullptr, epi);
+                          const ConvGeom& g, hipStream_t stream, float* stats,
+                          const EpiInfer* epi) {
+    if (epi != nullptr)
+        launch_cfg<CONV_STEM, 256, 64, 1, 2, BK, EpiInfer>(
+            src, wgt, out, g, 1, stream, nullptr, nullptr, nullptr, *epi);
+    else
+        launch_cfg<CONV_STEM, 256, 64, 1>(src, wgt, out, g, 1, stream, stats,
+                                          nullptr, nullptr);
 }
 
 static bool conv_bk32() {
     // BK=32 x NBUF=3 rings (FLUXDIST_CONV_BK32, 0 = off, default 1 = on,
-    // gated by grid fill in conv_dispatch). 128x128: 48 KB LDS/block -> 3
+    // gated by grid fill in conv_igemm_plan). 128x128: 48 KB LDS/block -> 3
     // blocks/CU (12 waves) vs the BK64 default's 2; measured -9..-28% on
     // the big-M layer-1/2 legs, +17% on the small-M 14x14 legs (294 blocks
     // can't feed 3 blocks/CU — profiles/ab_conv8.md addendum), hence the
@@ -784,106 +762,79 @@ static bool conv_bk32() {
     return v;
 }
 
-// tile geometry: a function of the output channel count alone
-static void conv_tile(int OC, int* bm, int* bn) {
-    const bool big = OC % 128 == 0;
-    *bm = big ? 128 : 256;
-    *bn = big ? 128 : 64;
-}
-
-// One place that decides tile geometry + split-K for a conv launch; the
-// torch bindings call this so the stats/skpart workspace shapes always
-// match what the kernel will write (the launcher takes BM/BN from the same
-// conv_tile and SK from its caller).
-//   M   = output rows (per z-class for dgrad), OC = output channels,
-//   T   = K-loop depth in BK=64 steps (nR*nS*RC/64), zbase = sy*sx classes
-//         for strided dgrad else 1.
-// split-K only when the launch would underfill the 256-CU chip AND the
-// K-loop is deep enough to amortize the fp32 partial round-trip (T < 48
-// measured a net loss: 14x14 / 1x1 shapes regressed up to 3x on a blanket
-// trigger — the 4-6x slab traffic dominates at shallow T, those legs are
-// traffic-bound, not fill-bound).
-void conv_igemm_plan(long M, int OC, long T, int zbase,
-                     int* bm, int* bn, int* sk) {
-    conv_tile(OC, bm, bn);
-    *sk = 1;
-    if (T >= 48) {
-        const long blocks = ((M + *bm - 1) / *bm) * (OC / *bn) * zbase;
-        if (blocks < 192) *sk = 4;
-        else if (blocks < 384) *sk = 2;
+// The one place that decides tile geometry, split-K and ring for a conv
+// launch, and with them the grid and the workspace shapes.
+ConvPlan conv_igemm_plan(const ConvGeom& g, ConvMode mode) {
+    const int OC = g.oc(mode);
+    const long M = g.rows(mode);
+    ConvPlan p;
+    // tile geometry: a function of the output channel count alone (the
+    // stem has the 256x64 kernel only)
+    const bool big = OC % 128 == 0 && mode != CONV_STEM;
+    p.bm = big ? 128 : 256;
+    p.bn = big ? 128 : 64;
+    const long mtiles = (M + p.bm - 1) / p.bm;
+    const long blocks1 = mtiles * (OC / p.bn) * g.classes(mode);
+    // split-K only when the launch would underfill the 256-CU chip AND the
+    // K-loop is deep enough to amortize the fp32 partial round-trip (T < 48
+    // measured a net loss: 14x14 / 1x1 shapes regressed up to 3x on a
+    // blanket trigger — the 4-6x slab traffic dominates at shallow T, those
+    // legs are traffic-bound, not fill-bound). Never for the stem, nor for
+    // a strided dgrad, whose parity classes already fan out (and whose
+    // partials would not be linear in m).
+    p.sk = 1;
+    if (mode != CONV_STEM && g.classes(mode) == 1 && g.depth(mode) >= 48) {
+        if (blocks1 < 192) p.sk = 4;
+        else if (blocks1 < 384) p.sk = 2;
     }
-}
-
-// The BK32 rings need the grid to fill their blocks/CU: >= ~576 blocks at
-// 3 blocks/CU (128x128), >= 512 at 2 (256x64); below that the lost
-// per-block depth outweighs the extra overlap.
-bool conv_igemm_ring(long blocks, int bn) {
-    return conv_bk32() && blocks >= (bn == 128 ? 576 : 512);
+    p.blocks = blocks1 * p.sk;
+    // The BK32 rings need the grid to fill their blocks/CU: >= ~576 blocks
+    // at 3 blocks/CU (128x128), >= 512 at 2 (256x64); below that the lost
+    // per-block depth outweighs the extra overlap.
+    p.ring = mode != CONV_STEM && conv_bk32() &&
+             p.blocks >= (p.bn == 128 ? 576 : 512);
+    p.stats_rows = mode == CONV_DGRAD ? 0
+                 : p.sk > 1 ? conv_skcombine_blocks(M, OC) : mtiles;
+    return p;
 }
 
 template <int MODE, class... EPI>
 static void conv_dispatch(const void* src, const void* wgt, void* out,
-                          int N, int H, int W, int C, int K, int P, int Q,
-                          int R, int S, int sy, int sx, int py, int px,
+                          const ConvGeom& g, const ConvPlan& p,
                           hipStream_t stream, float* stats, float* skpart,
-                          int SK, const void* accsrc, EPI... epi) {
-    constexpr bool dgrad = MODE == CONV_DGRAD;
-    const int OC = dgrad ? C : K;
-    const long Mv = !dgrad
-        ? (long)N * P * Q
-        : (long)N * ((H + sy - 1) / sy) * ((W + sx - 1) / sx);
-    const long zbase = dgrad ? sy * sx : 1;
-    int BM, BN;
-    conv_tile(OC, &BM, &BN);
-    const long blocks = ((Mv + BM - 1) / BM) * (OC / BN) * zbase * SK;
-    if (BN == 128) {
-        if (conv_igemm_ring(blocks, BN))
+                          const void* accsrc, EPI... epi) {
+    if (p.bn == 128) {
+        if (p.ring)
             launch_cfg<MODE, 128, 128, 2, 3, 32, EPI...>(
-                src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
-                stream, stats, skpart, SK, accsrc, epi...);
+                src, wgt, out, g, p.sk, stream, stats, skpart, accsrc, epi...);
         else
             launch_cfg<MODE, 128, 128, 2, 2, BK, EPI...>(
-                src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
-                stream, stats, skpart, SK, accsrc, epi...);
+                src, wgt, out, g, p.sk, stream, stats, skpart, accsrc, epi...);
     } else {
-        if (conv_igemm_ring(blocks, BN))
+        if (p.ring)
             launch_cfg<MODE, 256, 64, 1, 3, 32, EPI...>(
-                src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
-                stream, stats, skpart, SK, accsrc, epi...);
+                src, wgt, out, g, p.sk, stream, stats, skpart, accsrc, epi...);
         else
             launch_cfg<MODE, 256, 64, 1, 2, BK, EPI...>(
-                src, wgt, out, N, H, W, C, K, P, Q, R, S, sy, sx, py, px,
-                stream, stats, skpart, SK, accsrc, epi...);
+                src, wgt, out, g, p.sk, stream, stats, skpart, accsrc, epi...);
     }
 }
 
 void conv_igemm_launch(const void* src, const void* wgt, void* out,
-                       int N, int H, int W, int C, int K, int P, int Q,
-                       int R, int S, int sy, int sx, int py, int px,
-                       bool dgrad, hipStream_t stream, float* stats,
-                       float* skpart, int SK, const void* accsrc) {
-    if (dgrad)
-        conv_dispatch<CONV_DGRAD>(src, wgt, out, N, H, W, C, K, P, Q, R, S,
-                                  sy, sx, py, px, stream, stats, skpart, SK,
-                                  accsrc);
+                       const ConvGeom& g, ConvMode mode, const ConvPlan& plan,
+                       hipStream_t stream, float* stats, float* skpart,
+                       const void* accsrc, const EpiInfer* epi) {
+    assert(epi == nullptr || (mode == CONV_FWD && stats == nullptr &&
+                              accsrc == nullptr));
+    if (mode == CONV_DGRAD)
+        conv_dispatch<CONV_DGRAD>(src, wgt, out, g, plan, stream, stats,
+                                  skpart, accsrc);
+    else if (epi != nullptr && plan.sk == 1)
+        conv_dispatch<CONV_FWD, EpiInfer>(src, wgt, out, g, plan, stream,
+                                          nullptr, nullptr, nullptr, *epi);
     else
-        conv_dispatch<CONV_FWD>(src, wgt, out, N, H, W, C, K, P, Q, R, S,
-                                sy, sx, py, px, stream, stats, skpart, SK,
+        conv_dispatch<CONV_FWD>(src, wgt, out, g, plan, stream, stats, skpart,
                                 accsrc);
-}
-
-// forward with the inference epilogue (SK == 1 shapes; split-K shapes run
-// the plain forward into fp32 partials and conv_skcombine_fused_launch)
-void conv_igemm_fwd_fused_launch(const void* src, const void* wgt, void* out,
-                                 int N, int H, int W, int C, int K, int P,
-                                 int Q, int R, int S, int sy, int sx, int py,
-                                 int px, const float* scale,
-                                 const float* shift, const void* residual,
-                                 bool relu, hipStream_t stream) {
-    const EpiInfer epi{scale, shift, (const unsigned short*)residual, relu};
-    conv_dispatch<CONV_FWD, EpiInfer>(src, wgt, out, N, H, W, C, K, P, Q, R,
-                                      S, sy, sx, py, px, stream, nullptr,
-                                      nullptr, 1, nullptr, epi);
 }
 
 // ---- batched conv-weight transpose ----------------------------------------
@@ -1170,21 +1121,19 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(
 }
 
 void conv_stem_wgrad_launch(const void* dy, const void* x, float* ws,
-                            int N, int Hp, int Wp, int K, int P, int Q,
-                            int R, int sy, int sx, hipStream_t stream) {
-    // dy [M][K]; x padded C=8 image; ws [K][R*64] fp32 pre-zeroed.
+                            const ConvGeom& g, hipStream_t stream) {
     // Output is tiny (K x R*64), so small chunks would hammer the same
     // fp32 addresses with atomics (588 hits/address measured at 2048):
     // use 16k-pixel chunks.
-    const long M = (long)N * P * Q;
+    const long M = g.rows(CONV_STEM);
     constexpr int STEM_MCH = 8 * WG_MCH;    // 16k pixels: balances atomic fan-in per address against block count (32k measured 472 us/step vs 254 at 16k)
     const int nch = (int)((M + STEM_MCH - 1) / STEM_MCH);
-    dim3 grid((unsigned)(K / 64), 1u, (unsigned)(R * nch));
+    dim3 grid((unsigned)(g.K / 64), 1u, (unsigned)(g.R * nch));
     const size_t shmem = 3 * 2 * (WG_BM * 64) * sizeof(unsigned short);
     hipLaunchKernelGGL((conv_wgrad_kernel<2, true>), grid, dim3(256), shmem,
                        stream, (const unsigned short*)dy,
-                       (const unsigned short*)x, ws, N, Hp, Wp, 64, K, P, Q,
-                       R, 1, sy, sx, 0, 0, nch, STEM_MCH);
+                       (const unsigned short*)x, ws, g.N, g.H, g.W, 64, g.K,
+                       g.P, g.Q, g.R, 1, g.sy, g.sx, 0, 0, nch, STEM_MCH);
 }
 
 // pick the pixel-chunk size so the grid lands near `target` blocks:
@@ -1217,29 +1166,25 @@ static void conv_wgrad_plan(long M, int C, int K, int R, int S,
 }
 
 void conv_wgrad_launch(const void* dy, const void* x, float* ws,
-                       int N, int H, int W, int C, int K, int P, int Q,
-                       int R, int S, int sy, int sx, int py, int px,
-                       hipStream_t stream) {
-    const long M = (long)N * P * Q;
+                       const ConvGeom& g, hipStream_t stream) {
     int FTp, mch, nch;
-    conv_wgrad_plan(M, C, K, R, S, &FTp, &mch, &nch);
-    if (FTp == 4) {
-        dim3 grid((unsigned)(K / 128), (unsigned)(C / 128),
-                  (unsigned)(R * S * nch));
-        const size_t shmem = 2 * 2 * (WG_BM * 128) * sizeof(unsigned short);
-        hipLaunchKernelGGL(conv_wgrad_kernel<4>, grid, dim3(256), shmem,
-                           stream, (const unsigned short*)dy,
-                           (const unsigned short*)x, ws, N, H, W, C, K,
-                           P, Q, R, S, sy, sx, py, px, nch, mch);
-    } else {
-        dim3 grid((unsigned)(K / 64), (unsigned)(C / 64),
-                  (unsigned)(R * S * nch));
-        const size_t shmem = 3 * 2 * (WG_BM * 64) * sizeof(unsigned short);
-        hipLaunchKernelGGL(conv_wgrad_kernel<2>, grid, dim3(256), shmem,
-                           stream, (const unsigned short*)dy,
-                           (const unsigned short*)x, ws, N, H, W, C, K,
-                           P, Q, R, S, sy, sx, py, px, nch, mch);
-    }
+    conv_wgrad_plan(g.rows(CONV_FWD), g.C, g.K, g.R, g.S, &FTp, &mch, &nch);
+    // one argument list for both tile sizes
+    auto launch = [&](auto kern, int tch, size_t shmem) {
+        dim3 grid((unsigned)(g.K / tch), (unsigned)(g.C / tch),
+                  (unsigned)(g.R * g.S * nch));
+        hipLaunchKernelGGL(kern, grid, dim3(256), shmem, stream,
+                           (const unsigned short*)dy,
+                           (const unsigned short*)x, ws, g.N, g.H, g.W, g.C,
+                           g.K, g.P, g.Q, g.R, g.S, g.sy, g.sx, g.py, g.px,
+                           nch, mch);
+    };
+    if (FTp == 4)
+        launch(conv_wgrad_kernel<4>, 128,
+               2 * 2 * (WG_BM * 128) * sizeof(unsigned short));
+    else
+        launch(conv_wgrad_kernel<2>, 64,
+               3 * 2 * (WG_BM * 64) * sizeof(unsigned short));
 }
 
 }  // namespace fda

@@ -144,69 +144,90 @@ void gap_bwd_launch(const void* gy, void* gx, int N, int HW, int C, DT dt,
                     hipStream_t s);
 
 // Implicit-GEMM conv, NHWC bf16 only (see conv_igemm.hip).
+enum ConvMode { CONV_FWD = 0, CONV_DGRAD = 1, CONV_STEM = 2 };
+
+// One conv's geometry, in the forward's terms for every mode: x [N,H,W,C],
+// w [K][R][S][C], y [N,P,Q,K]. CONV_STEM: H, W are the padded image's, C = 8,
+// S = 1 (taps iterate r only), no padding.
+struct ConvGeom {
+    int N, H, W, C, K, P, Q, R, S, sy, sx, py, px;
+    // output channels
+    int oc(ConvMode m) const { return m == CONV_DGRAD ? C : K; }
+    // dgrad launches one z-class per (h % sy, w % sx) parity
+    int classes(ConvMode m) const { return m == CONV_DGRAD ? sy * sx : 1; }
+    // output rows M (dgrad: of the largest parity class)
+    long rows(ConvMode m) const {
+        return m == CONV_DGRAD
+            ? (long)N * ((H + sy - 1) / sy) * ((W + sx - 1) / sx)
+            : (long)N * P * Q;
+    }
+    // K-loop depth T in BK=64 steps (dgrad: over the whole filter, which is
+    // what a stride-1 dgrad iterates)
+    long depth(ConvMode m) const {
+        return m == CONV_STEM ? R : (long)R * S * ((m == CONV_DGRAD ? K : C) / 64);
+    }
+};
+
+// What a launch of that geometry runs: tile, split-K factor, BK32 3-buffer
+// ring or BK64 2-buffer, grid size (all z-classes and split-K slices), and
+// the row count of the BN stats partials [stats_rows][2][OC] a forward
+// writes (m-tiles, or the combine kernel's blocks when sk > 1). The launcher
+// obeys it and the bindings size skpart [sk][M][OC] and the partials from
+// it, so workspace shapes always match what the kernels write.
+struct ConvPlan {
+    int bm, bn, sk;
+    bool ring;
+    long blocks;
+    long stats_rows;
+};
+ConvPlan conv_igemm_plan(const ConvGeom& g, ConvMode mode);
+
+// Inference epilogue: eval BN + residual + ReLU on the fp32 accumulator,
+//   y = bf16(relu(fma(acc, scale[k], shift[k]) + residual[m][k]))
+// rounded once. scale/shift: OC floats, 16-B aligned; residual: bf16 in the
+// output's layout, 16-B aligned, or null.
+struct EpiInfer {
+    const float* scale;
+    const float* shift;
+    const unsigned short* residual;
+    int relu;
+};
+
 // fwd:   src=x [N,H,W,C], wgt=w [K][R*S*C], out=y [N*P*Q][K]
 // dgrad: src=dy [N,P,Q,K], wgt=wt [R*S*C][K] (pre-transposed), out=dx
+// plan.sk > 1: skpart receives the fp32 partials and nothing else is
+// written; conv_skcombine_launch then folds them into `out` and takes the
+// stats / accsrc / epi arguments instead. accsrc: bf16 in the output's
+// layout, added before the round. epi: forward only, and it excludes stats
+// and accsrc (the inference kernels have neither), here and in the combine
+// and stem launchers.
 void conv_igemm_launch(const void* src, const void* wgt, void* out,
-                       int N, int H, int W, int C, int K, int P, int Q,
-                       int R, int S, int sy, int sx, int py, int px,
-                       bool dgrad, hipStream_t stream,
-                       float* stats = nullptr, float* skpart = nullptr,
-                       int SK = 1, const void* accsrc = nullptr);
+                       const ConvGeom& g, ConvMode mode, const ConvPlan& plan,
+                       hipStream_t stream, float* stats = nullptr,
+                       float* skpart = nullptr, const void* accsrc = nullptr,
+                       const EpiInfer* epi = nullptr);
 
-// Tile/split-K plan for a conv launch — the single source of truth the
-// bindings use to size the stats/skpart workspaces. M = output rows (per
-// z-class for dgrad), OC = output channels, T = K-loop depth in BK=64
-// steps, zbase = sy*sx for strided dgrad else 1.
-void conv_igemm_plan(long M, int OC, long T, int zbase,
-                     int* bm, int* bn, int* sk);
-
-// True when a launch of `blocks` blocks (all z and split-K slices counted)
-// with tile width bn takes the BK32 3-buffer ring instead of BK64 2-buffer.
-bool conv_igemm_ring(long blocks, int bn);
-
-// split-K combine: y = bf16(sum over SK fp32 partials) + optional BN
-// stats partials ([nblocks][2][OC])
-int conv_skcombine_blocks(long M, int OC);
+// split-K combine: y = bf16(sum over SK fp32 partials [SK][M][OC]), with
+// optional BN stats partials [plan.stats_rows][2][OC], accsrc or inference
+// epilogue. OC <= 2048.
 void conv_skcombine_launch(const float* part, void* y, float* stats, long M,
-                           int OC, int SK, int nblocks, hipStream_t stream,
-                           const void* accsrc = nullptr);
+                           int OC, int SK, hipStream_t stream,
+                           const void* accsrc = nullptr,
+                           const EpiInfer* epi = nullptr);
 
-// stem conv (small C via channel-pad to 8, spatially pre-padded input)
+// stem conv (small C via channel-pad to 8, spatially pre-padded input):
+// src [N,Hp,Wp,8], wgt wpad [K][R][64], out [N*P*Q][K]; g as CONV_STEM
 void conv_stem_fwd_launch(const void* src, const void* wgt, void* out,
-                          int N, int Hp, int Wp, int K, int P, int Q,
-                          int R, int sy, int sx, hipStream_t stream,
-                          float* stats = nullptr);
+                          const ConvGeom& g, hipStream_t stream,
+                          float* stats = nullptr,
+                          const EpiInfer* epi = nullptr);
+// dy [M][K]; x as above; ws [K][R*64] fp32 pre-zeroed
 void conv_stem_wgrad_launch(const void* dy, const void* x, float* ws,
-                            int N, int Hp, int Wp, int K, int P, int Q,
-                            int R, int sy, int sx, hipStream_t stream);
-
-// Inference forward: eval BN + residual + ReLU in the conv epilogue,
-//   y = bf16(relu(fma(acc, scale[k], shift[k]) + residual[m][k]))
-// from the fp32 accumulator, rounded once. scale/shift: K floats; residual:
-// bf16 in y's layout or null. The fwd launcher serves SK == 1 plans; for
-// SK > 1 run conv_igemm_launch into fp32 partials and fold them with
-// conv_skcombine_fused_launch, which applies the same epilogue.
-void conv_igemm_fwd_fused_launch(const void* src, const void* wgt, void* out,
-                                 int N, int H, int W, int C, int K, int P,
-                                 int Q, int R, int S, int sy, int sx, int py,
-                                 int px, const float* scale,
-                                 const float* shift, const void* residual,
-                                 bool relu, hipStream_t stream);
-void conv_skcombine_fused_launch(const float* part, void* y, long M, int OC,
-                                 int SK, int nblocks, const float* scale,
-                                 const float* shift, const void* residual,
-                                 bool relu, hipStream_t stream);
-void conv_stem_fwd_fused_launch(const void* src, const void* wgt, void* out,
-                                int N, int Hp, int Wp, int K, int P, int Q,
-                                int R, int sy, int sx, const float* scale,
-                                const float* shift, bool relu,
-                                hipStream_t stream);
+                            const ConvGeom& g, hipStream_t stream);
 
 // wgrad: ws[K][RS*C] fp32 (pre-zeroed) += dy^T @ im2col(x), atomic chunks.
 void conv_wgrad_launch(const void* dy, const void* x, float* ws,
-                       int N, int H, int W, int C, int K, int P, int Q,
-                       int R, int S, int sy, int sx, int py, int px,
-                       hipStream_t stream);
+                       const ConvGeom& g, hipStream_t stream);
 
 // batched conv-weight transpose: w[k][rc] -> wt[rc][k] for all tensors in
 // one launch (device pointer arrays)

@@ -29,7 +29,8 @@ import torch.nn as nn
 
 from .models.resnet import (BasicBlock, Bottleneck, Downsample, FusedBNAct,
                             ResNet)
-from .ops.conv import FdaConv2d, _native_supported, _stem_supported, fda_conv2d
+from .ops.conv import (FdaConv2d, _native_supported, _stem_supported,
+                       fda_conv2d, pack_stem_operands, stem_buffer_key)
 from .ops.functional import (GlobalAvgPool, MaxPool2d, batch_norm_act,
                              batch_norm_act_pool)
 from .ops.linear import FdaLinear
@@ -262,30 +263,14 @@ class InferenceModel:
     def _stem_fused(self, p: _Pair, x, scale, shift):
         C = require_native("conv_stem_fwd_fused")
         conv = p.conv
-        weight = conv.weight
-        K, Cin, R, S = weight.shape
-        sy, sx = conv.stride
-        py, px = conv.padding
-        N, _, H, W = x.shape
-        P = (H + 2 * py - R) // sy + 1
-        Q = (W + 2 * px - S) // sx + 1
-        # channel-pad to 8 and pre-pad spatially, as ops/conv.py's stem
-        # does; the buffer is this object's own, so a captured graph keeps
+        # the padded buffer is this object's own, so a captured graph keeps
         # replaying into memory nobody else checks out
-        key = (N, Cin, H, W, py, px, x.device)
-        x8 = self._x8.get(key)
-        if x8 is None:
-            x8 = torch.empty(N, 8, H + 2 * py, W + 2 * px + 8, dtype=x.dtype,
-                             device=x.device,
-                             memory_format=torch.channels_last).zero_()
-            self._x8[key] = x8
-        x8[:, :Cin, py:py + H, px:px + W] = x
-        wpad = torch.zeros(K, R, 64, dtype=weight.dtype, device=weight.device)
-        wpad.view(K, R, 8, 8)[:, :, :S, :Cin] = (
-            weight.contiguous(memory_format=torch.channels_last)
-            .permute(0, 2, 3, 1))
-        return C.conv_stem_fwd_fused(x8, wpad, scale, shift, p.bn.relu, R,
-                                     sy, sx, P, Q)
+        key = stem_buffer_key(x, conv.weight, conv.padding)
+        x8, wpad, P, Q = pack_stem_operands(x, conv.weight, conv.stride,
+                                            conv.padding, self._x8.get(key))
+        self._x8[key] = x8
+        return C.conv_stem_fwd_fused(x8, wpad, scale, shift, p.bn.relu,
+                                     conv.weight.shape[2], *conv.stride, P, Q)
 
     def _run_pair(self, p: _Pair, x, residual=None, fuse=False):
         conv, bn = p.conv, p.bn

@@ -363,6 +363,37 @@ class _FdaConv2d(torch.autograd.Function):
         return dx, dw, None, None, None
 
 
+def stem_buffer_key(x, weight, padding):
+    """What a padded stem input buffer is reused by: its shape and device."""
+    N, _, H, W = x.shape
+    return (N, weight.shape[1], H, W, *padding, x.device)
+
+
+def pack_stem_operands(x, weight, stride, padding, x8=None):
+    """Operands of the CONV_STEM kernels: (x8, wpad, P, Q).
+
+    x8 [N,8,H+2py,W+2px+8] is x channel-padded to 8 and spatially pre-padded
+    by (py, px), with 8 columns of right-edge slack so the 8-pixel (s=0..7)
+    granule row never leaves the image. Pass a buffer of a previous call
+    with the same `stem_buffer_key` to reuse it: its zero border survives,
+    so only the interior is rewritten. wpad [K][R][64] is the weight as
+    [K][R][s<8][c<8], zero where s >= S or c >= Cin."""
+    K, Cin, R, S = weight.shape
+    sy, sx = stride
+    py, px = padding
+    N, _, H, W = x.shape
+    if x8 is None:
+        x8 = torch.empty(N, 8, H + 2 * py, W + 2 * px + 8, dtype=x.dtype,
+                         device=x.device,
+                         memory_format=torch.channels_last).zero_()
+    x8[:, :Cin, py : py + H, px : px + W] = x
+    wpad = torch.zeros(K, R, 64, dtype=weight.dtype, device=weight.device)
+    wpad.view(K, R, 8, 8)[:, :, :S, :Cin] = (
+        weight.contiguous(memory_format=torch.channels_last)
+        .permute(0, 2, 3, 1))  # [K][R][S][C]
+    return (x8, wpad, (H + 2 * py - R) // sy + 1, (W + 2 * px - S) // sx + 1)
+
+
 class _FdaStemConv2d(torch.autograd.Function):
     """Small-C stem conv (C<=5, S<=7): channel-pad to 8 + spatial pre-pad,
     then the CONV_STEM kernel (one K-step per filter row r — 8 pixels x 8
@@ -375,29 +406,14 @@ class _FdaStemConv2d(torch.autograd.Function):
         clear_conv_stats()
         K, Cin, R, S = weight.shape
         sy, sx = stride
-        py, px = padding
-        N, _, H, W = x.shape
-        P = (H + 2 * py - R) // sy + 1
-        Q = (W + 2 * px - S) // sx + 1
         xc = x.contiguous(memory_format=torch.channels_last)
-        # pad channels to 8 and spatial by (py, px); extra right-edge pixel
-        # slack so the 8-pixel (s=0..7) granule row never leaves the image.
-        # Padded buffers come from a per-shape free-list pool: the zero
-        # border survives reuse so each checkout only copies the interior,
-        # but the buffer is exclusively owned by THIS graph until backward
-        # returns it (no aliasing across forwards — round-1 ADVICE #1).
-        Wp = W + 2 * px + 8
-        key = (N, Cin, H, W, py, px, x.device)
-        x8 = _stem_pool_get(key)
-        if x8 is None:
-            x8 = torch.empty(N, 8, H + 2 * py, Wp, dtype=x.dtype,
-                             device=x.device,
-                             memory_format=torch.channels_last).zero_()
-        x8[:, :Cin, py : py + H, px : px + W] = xc
-        wpad = torch.zeros(K, R, 64, dtype=weight.dtype, device=weight.device)
-        wpad.view(K, R, 8, 8)[:, :, :S, :Cin] = (
-            weight.contiguous(memory_format=torch.channels_last)
-            .permute(0, 2, 3, 1))  # [K][R][S][C]
+        # Padded buffers come from a per-shape free-list pool: each
+        # checkout only copies the interior, but the buffer is exclusively
+        # owned by THIS graph until backward returns it (no aliasing across
+        # forwards — round-1 ADVICE #1).
+        key = stem_buffer_key(x, weight, padding)
+        x8, wpad, P, Q = pack_stem_operands(xc, weight, stride, padding,
+                                            _stem_pool_get(key))
         if want_stats:
             y, part = C.conv_stem_fwd_stats(x8, wpad, R, sy, sx, P, Q)
             stash_conv_stats(y, part)
