@@ -507,6 +507,150 @@ void adam_step(at::Tensor P, at::Tensor G, at::Tensor M, at::Tensor V,
                           dt_of(P), cur_stream());
 }
 
+// ---- LARS on the flat buffers (lars.hip) -----------------------------------
+
+// The chunk table of one flat group, on the host: segment i is the
+// parameter at `offsets[i]` with `numels[i]` own elements inside a buffer of
+// n elements, and gets the id seg_base + i. Each segment is tiled in order
+// by chunks of at most LARS_CHUNK elements, so every chunk starts a multiple
+// of 64 elements into its segment. Returns CPU int32 [nchunks][3].
+at::Tensor lars_plan(std::vector<int64_t> offsets, std::vector<int64_t> numels,
+                     int64_t n, int64_t seg_base) {
+    const char* op = "lars_plan";
+    static_assert(fda::LARS_CHUNK % 64 == 0, "chunks keep 64-element starts");
+    TORCH_CHECK(offsets.size() == numels.size(), op,
+                ": offsets and numels differ in length");
+    TORCH_CHECK(n >= 0 && n < ((int64_t)1 << 31), op,
+                ": the flat buffer must have fewer than 2^31 elements, got ",
+                n);
+    TORCH_CHECK(n % 64 == 0, op, ": the flat buffer must be padded to 64");
+    TORCH_CHECK(seg_base >= 0 &&
+                    seg_base + (int64_t)offsets.size() < ((int64_t)1 << 31),
+                op, ": bad seg_base ", seg_base);
+    int64_t end = 0, rows = 0;
+    for (size_t i = 0; i < offsets.size(); ++i) {
+        TORCH_CHECK(numels[i] >= 0, op, ": segment ", i, " has numel ",
+                    numels[i]);
+        TORCH_CHECK(offsets[i] % 64 == 0, op, ": segment ", i, " starts at ",
+                    offsets[i], ", not a multiple of 64");
+        TORCH_CHECK(offsets[i] >= end, op, ": segment ", i, " at ", offsets[i],
+                    " is unsorted or overlaps its predecessor, which ends at ",
+                    end);
+        TORCH_CHECK(offsets[i] <= n && numels[i] <= n - offsets[i], op,
+                    ": segment ", i, " reaches past the buffer's ", n,
+                    " elements");
+        end = offsets[i] + numels[i];
+        rows += (numels[i] + fda::LARS_CHUNK - 1) / fda::LARS_CHUNK;
+    }
+    auto table = at::empty({rows, fda::LARS_ROW_INTS},
+                           at::TensorOptions().dtype(at::kInt));
+    int32_t* r = table.data_ptr<int32_t>();
+    for (size_t i = 0; i < offsets.size(); ++i)
+        for (int64_t e = 0; e < numels[i]; e += fda::LARS_CHUNK) {
+            *r++ = (int32_t)(seg_base + (int64_t)i);
+            *r++ = (int32_t)(offsets[i] + e);
+            *r++ = (int32_t)std::min<int64_t>(fda::LARS_CHUNK, numels[i] - e);
+        }
+    return table;
+}
+
+// A group's chunk table; returns its row count.
+int64_t check_lars_table(const char* op, const at::Tensor& table) {
+    TORCH_CHECK(table.scalar_type() == at::kInt && table.dim() == 2 &&
+                    table.size(1) == fda::LARS_ROW_INTS &&
+                    table.is_contiguous(),
+                op, ": table must be contiguous int32 [nchunks][",
+                fda::LARS_ROW_INTS, "]");
+    return table.size(0);
+}
+
+// seg_meta int32 [S][3], coef fp32 [S], stats fp32 [2 + 2 S]; returns S.
+int64_t check_lars_segments(const char* op, const at::Tensor& seg_meta,
+                            const at::Tensor& coef, const at::Tensor& stats) {
+    TORCH_CHECK(seg_meta.scalar_type() == at::kInt && seg_meta.dim() == 2 &&
+                    seg_meta.size(1) == fda::LARS_SEG_INTS &&
+                    seg_meta.is_contiguous(),
+                op, ": seg_meta must be contiguous int32 [S][",
+                fda::LARS_SEG_INTS, "]");
+    const int64_t S = seg_meta.size(0);
+    check_flat(op, "coef", coef, at::kFloat, S);
+    check_flat(op, "stats", stats, at::kFloat, fda::LARS_STATS_HEAD + 2 * S);
+    return S;
+}
+
+// Sum w^2 / sum g^2 of every chunk of one flat group into rows
+// [chunk_base, chunk_base + nchunks) of partials (double [total_chunks][2]
+// flattened). S is the optimizer's segment count: rows naming a segment
+// beyond it are not trusted.
+void lars_norms(at::Tensor P, at::Tensor G, at::Tensor M, at::Tensor table,
+                at::Tensor partials, int64_t chunk_base, int64_t total_chunks,
+                int64_t S) {
+    const char* op = "lars_norms";
+    const bool has_master = check_optimizer_operands(op, P, G, M, {});
+    TORCH_CHECK(P.numel() % 64 == 0 && P.numel() < ((int64_t)1 << 31), op,
+                ": flat buffers must be padded to 64 and shorter than 2^31");
+    const int64_t nchunks = check_lars_table(op, table);
+    TORCH_CHECK(total_chunks >= 0 && total_chunks < ((int64_t)1 << 30), op,
+                ": bad total_chunks ", total_chunks);
+    check_flat(op, "partials", partials, at::kDouble, 2 * total_chunks);
+    TORCH_CHECK(chunk_base >= 0 && chunk_base + nchunks <= total_chunks, op,
+                ": chunks [", chunk_base, ", ", chunk_base + nchunks,
+                ") leave the ", total_chunks, " rows of partials");
+    TORCH_CHECK(S >= 0 && S < ((int64_t)1 << 31), op, ": bad S ", S);
+    check_device(op, {P, G, M, table, partials});
+    fda::lars_norms_launch(P.data_ptr(), G.data_ptr(), M.data_ptr<float>(),
+                           table.data_ptr<int32_t>(), (int)nchunks,
+                           partials.data_ptr<double>() + 2 * chunk_base,
+                           P.numel(), (int)S, has_master, dt_of(P),
+                           cur_stream());
+}
+
+// Fold all partials per segment, then gnorm, clip and coef_s = lr * trust_s;
+// bumps `skipped` when gnorm is not finite. lr is read on the device.
+void lars_fold(at::Tensor partials, at::Tensor seg_meta, at::Tensor lr,
+               at::Tensor coef, at::Tensor stats, at::Tensor skipped,
+               double eta, double weight_decay, double eps,
+               double max_grad_norm) {
+    const char* op = "lars_fold";
+    const int64_t S = check_lars_segments(op, seg_meta, coef, stats);
+    TORCH_CHECK(partials.scalar_type() == at::kDouble &&
+                    partials.is_contiguous() && partials.numel() % 2 == 0 &&
+                    partials.numel() < ((int64_t)1 << 31),
+                op, ": partials must be contiguous double with 2 elements "
+                "per chunk");
+    check_flat(op, "lr", lr, at::kFloat, 1);
+    check_flat(op, "skipped", skipped, at::kInt, 1);
+    check_device(op, {partials, seg_meta, lr, coef, stats, skipped});
+    fda::lars_fold_launch(partials.data_ptr<double>(),
+                          (int)(partials.numel() / 2),
+                          seg_meta.data_ptr<int32_t>(), (int)S,
+                          lr.data_ptr<float>(), (float)eta,
+                          (float)weight_decay, (float)eps,
+                          (float)max_grad_norm, coef.data_ptr<float>(),
+                          stats.data_ptr<float>(), skipped.data_ptr<int>(),
+                          cur_stream());
+}
+
+// The update of one flat group from the fold's coef / stats.
+void lars_step(at::Tensor P, at::Tensor G, at::Tensor M, at::Tensor V,
+               at::Tensor table, at::Tensor seg_meta, at::Tensor coef,
+               at::Tensor stats, double momentum, double weight_decay) {
+    const char* op = "lars_step";
+    const bool has_master = check_optimizer_operands(op, P, G, M, {V});
+    TORCH_CHECK(P.numel() % 64 == 0 && P.numel() < ((int64_t)1 << 31), op,
+                ": flat buffers must be padded to 64 and shorter than 2^31");
+    const int64_t nchunks = check_lars_table(op, table);
+    const int64_t S = check_lars_segments(op, seg_meta, coef, stats);
+    check_device(op, {P, G, M, V, table, seg_meta, coef, stats});
+    fda::lars_step_launch(P.data_ptr(), G.data_ptr(), M.data_ptr<float>(),
+                          V.data_ptr<float>(), table.data_ptr<int32_t>(),
+                          (int)nchunks, seg_meta.data_ptr<int32_t>(),
+                          coef.data_ptr<float>(), stats.data_ptr<float>(),
+                          P.numel(), (int)S, (float)momentum,
+                          (float)weight_decay, has_master, dt_of(P),
+                          cur_stream());
+}
+
 // Replica gradient mean, in place over the R flat G buffers of one dtype
 // group (parallel/flatsync.py). The kernel reads every buffer before it
 // writes any, per 16 B vector; an aliased pair would still race between
@@ -1154,6 +1298,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gap_bwd", &gap_bwd);
     m.def("sgd_step", &sgd_step);
     m.def("adam_step", &adam_step);
+    m.def("lars_plan", &lars_plan, pybind11::arg("offsets"),
+          pybind11::arg("numels"), pybind11::arg("n"),
+          pybind11::arg("seg_base"),
+          "host chunk table of one flat group: int32 [nchunks][3] rows of "
+          "{segment id, start element, own elements}");
+    m.def("lars_norms", &lars_norms, pybind11::arg("P"), pybind11::arg("G"),
+          pybind11::arg("M"), pybind11::arg("table"),
+          pybind11::arg("partials"), pybind11::arg("chunk_base"),
+          pybind11::arg("total_chunks"), pybind11::arg("S"));
+    m.def("lars_fold", &lars_fold, pybind11::arg("partials"),
+          pybind11::arg("seg_meta"), pybind11::arg("lr"),
+          pybind11::arg("coef"), pybind11::arg("stats"),
+          pybind11::arg("skipped"), pybind11::arg("eta"),
+          pybind11::arg("weight_decay"), pybind11::arg("eps"),
+          pybind11::arg("max_grad_norm"));
+    m.def("lars_step", &lars_step, pybind11::arg("P"), pybind11::arg("G"),
+          pybind11::arg("M"), pybind11::arg("V"), pybind11::arg("table"),
+          pybind11::arg("seg_meta"), pybind11::arg("coef"),
+          pybind11::arg("stats"), pybind11::arg("momentum"),
+          pybind11::arg("weight_decay"));
+    m.attr("LARS_CHUNK") = fda::LARS_CHUNK;
     m.def("grad_mean_multi", &grad_mean_multi, pybind11::arg("grads"),
           pybind11::arg("flag") = pybind11::none(),
           "in-place mean of R flat gradient buffers (fp32 sum, one round)");

@@ -285,6 +285,37 @@ void adam_step_launch(void* P, const void* G, float* M, float* V, float* S,
                       float wd, float bc1, float bc2, bool has_master, DT dt,
                       hipStream_t s);
 
+// LARS over the flat buffers (lars.hip). A segment is one parameter's slice;
+// segments are numbered over all flat groups of an optimizer, S in total.
+//   table:    this group's chunk table, nchunks rows of LARS_ROW_INTS int32
+//             {segment id, start element in the group buffer, count of the
+//             parameter's own elements}; count <= LARS_CHUNK, start % 64 == 0.
+//   seg_meta: S rows of LARS_SEG_INTS int32 {first chunk, end chunk, flags}
+//             over the concatenated tables; flag bit 0 = adapt, bit 1 = decay.
+//   partials: {sum w^2, sum g^2} per chunk (double). norms writes this
+//             group's nchunks rows; fold reads all total_chunks rows.
+//   stats:    fp32 {gnorm, clip, W_0..W_S-1, G_0..G_S-1}; coef: fp32 [S].
+//   lr:       one fp32 in device memory, read by the fold kernel.
+// A table or seg_meta row the kernels cannot trust gives NaN sums, hence a
+// non-finite gnorm, hence a step that writes nothing and bumps *skipped.
+constexpr int LARS_CHUNK = 4096;
+constexpr int LARS_ROW_INTS = 3;
+constexpr int LARS_SEG_INTS = 3;
+constexpr int LARS_STATS_HEAD = 2;
+void lars_norms_launch(const void* P, const void* G, const float* M,
+                       const int32_t* table, int nchunks, double* partials,
+                       int64_t n, int S, bool has_master, DT dt,
+                       hipStream_t s);
+void lars_fold_launch(const double* partials, int total_chunks,
+                      const int32_t* seg_meta, int S, const float* lr,
+                      float eta, float wd, float eps, float max_grad_norm,
+                      float* coef, float* stats, int* skipped, hipStream_t s);
+void lars_step_launch(void* P, const void* G, float* M, float* V,
+                      const int32_t* table, int nchunks,
+                      const int32_t* seg_meta, const float* coef,
+                      const float* stats, int64_t n, int S, float mom,
+                      float wd, bool has_master, DT dt, hipStream_t s);
+
 // Replica gradient mean (task-DDP flat sync): bufs is a HOST array of R
 // device pointers (1 <= R <= GRAD_MEAN_MAX_R) to disjoint, 16 B-aligned flat
 // buffers of n elements, n % V == 0. Each becomes

@@ -19,6 +19,8 @@ from .functional import (  # noqa: F401
     global_avg_pool,
     GlobalAvgPool,
 )
-from .fused_optim import FusedSGDMomentum, FusedAdam  # noqa: F401
+from .fused_optim import (  # noqa: F401
+    FusedSGDMomentum, FusedAdam, FusedLARS, flat_grad_norm,
+)
 from .conv import fda_conv2d, FdaConv2d  # noqa: F401
 from .linear import FdaLinear  # noqa: F401

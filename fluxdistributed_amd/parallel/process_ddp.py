@@ -95,6 +95,15 @@ class DDPModel(torch.nn.Module):
             self.bucketer.allreduce_now()
 
 
+def log_grad_health(optimizer):
+    """Log points only (both reads synchronize): the latest gradient norm
+    and the skipped-step count of an optimizer that tracks them."""
+    if hasattr(optimizer, "last_grad_norm"):
+        log.info("grad_norm=%.4e skipped_steps=%d lr=%.4e",
+                 float(optimizer.last_grad_norm()), optimizer.skipped_steps(),
+                 optimizer.param_groups[0]["lr"])
+
+
 def syncgrads_worker(
     model: torch.nn.Module,
     optimizer: _FlatOptimizer,
@@ -108,10 +117,17 @@ def syncgrads_worker(
     should_stop: Optional[Callable[[int], bool]] = None,
     bucket_cap_mb: float = 25.0,
     fused_eval: bool = False,
+    sched: Optional[Callable[[int], None]] = None,
+    log_every: int = 0,
 ):
     """Per-rank training loop — the `getgrads` worker + `syncgrads` reducer
     of the reference collapsed into symmetric all-reduce ranks
     (/root/reference/src/sync.jl:83-170 and :36-81).
+
+    `sched(step)` is called once after every step with the number of steps
+    done, as train() in task mode does. `log_every` > 0 logs the loss on
+    rank 0 at that cadence, and the gradient norm and skipped-step count of
+    an optimizer that has them (FusedLARS).
 
     Returns (model, optimizer, stats). Checkpoints (rank 0 only) follow the
     reference cadence knob (every `checkpoint_every` steps when > 0;
@@ -138,6 +154,12 @@ def syncgrads_worker(
         with timers.stage("optimizer"):
             optimizer.step()
         thr.add(int(x.shape[0]) * ddp.world)
+        if sched is not None:
+            sched(step + 1)
+        if log_every and (step + 1) % log_every == 0 and rank == 0:
+            log.info("step %d loss=%.4f imgs/s=%.1f", step + 1, float(loss),
+                     thr.rate())
+            log_grad_health(optimizer)
 
         if val is not None and val_every and (step + 1) % val_every == 0 and rank == 0:
             from .task_ddp import log_loss_and_acc, Replica

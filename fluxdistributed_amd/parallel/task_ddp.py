@@ -261,6 +261,9 @@ def train(
             log.info("cycle %d loss=%.4f imgs/s=%.1f", state.cycles,
                      sum(lv) / max(len(lv), 1), state.throughput.rate())
             # the loss read above has synchronized already
+            from .process_ddp import log_grad_health
+
+            log_grad_health(reps[0].optimizer)
             if state.reducer is not None and state.reducer.pop_nonfinite():
                 state.nonfinite_steps += 1
                 log.warning("non-finite gradient mean seen by cycle %d "

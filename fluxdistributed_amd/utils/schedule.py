@@ -24,6 +24,36 @@ def step_decay(opt, base_lr: float, factor: float = 0.2, every: int = 10) -> Cal
     return sched
 
 
+def warmup_poly_lr(cycle: int, base_lr: float, warmup_cycles: int,
+                   total_cycles: int, power: float = 2.0,
+                   min_lr: float = 0.0) -> float:
+    """Linear ramp 0 -> base_lr over `warmup_cycles`, then
+    min_lr + (base_lr - min_lr) * (1 - t)^power with t running 0 -> 1 from
+    the end of warm-up to `total_cycles` (the LARS large-batch schedule)."""
+    if cycle < warmup_cycles:
+        return base_lr * cycle / warmup_cycles
+    span = max(1, total_cycles - warmup_cycles)
+    t = min((cycle - warmup_cycles) / span, 1.0)
+    return min_lr + (base_lr - min_lr) * (1.0 - t) ** power
+
+
+def warmup_poly(opt, base_lr: float, warmup_cycles: int, total_cycles: int,
+                power: float = 2.0, min_lr: float = 0.0) -> Callable[[int], float]:
+    """`sched(cycle)` sets and returns warmup_poly_lr(cycle, ...). An
+    optimizer with a device-side learning rate (`set_lr`, FusedLARS) gets it
+    written there as well, so the next replay of a captured step uses it."""
+
+    def sched(cycle: int):
+        lr = warmup_poly_lr(cycle, base_lr, warmup_cycles, total_cycles,
+                            power, min_lr)
+        _set_lr(opt, lr)
+        if hasattr(opt, "set_lr"):
+            opt.set_lr(lr)
+        return lr
+
+    return sched
+
+
 def cosine(opt, base_lr: float, total_cycles: int, min_lr: float = 0.0) -> Callable[[int], None]:
     def sched(cycle: int):
         t = min(cycle / max(1, total_cycles), 1.0)

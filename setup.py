@@ -24,6 +24,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "pool.hip"),
         os.path.join(CSRC, "conv_igemm.hip"),
         os.path.join(CSRC, "preprocess.hip"),
+        os.path.join(CSRC, "lars.hip"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],

@@ -21,7 +21,9 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from fluxdistributed_amd.models import build_model
-from fluxdistributed_amd.ops import FusedSGDMomentum, FusedAdam, logit_cross_entropy
+from fluxdistributed_amd.ops import (
+    FusedSGDMomentum, FusedAdam, FusedLARS, logit_cross_entropy,
+)
 from fluxdistributed_amd.parallel.task_ddp import prepare_training, train
 from fluxdistributed_amd.parallel.process_ddp import init_process_group, syncgrads_worker
 from fluxdistributed_amd.data.synthetic import SyntheticBatcher
@@ -47,9 +49,21 @@ def parse_args():
     p.add_argument("--image-size", type=int, default=224)
     p.add_argument("--dtype", default="bf16" if torch.cuda.is_available() else "fp32",
                    choices=["bf16", "fp32"])
-    p.add_argument("--optimizer", choices=["momentum", "adam"], default="momentum")
+    p.add_argument("--optimizer", choices=["momentum", "adam", "lars"],
+                   default="momentum")
     p.add_argument("--lr", type=float, default=0.01)
     p.add_argument("--momentum", type=float, default=0.9)
+    p.add_argument("--weight-decay", type=float, default=5e-5,
+                   help="lars: weight decay (kept off 1-D parameters)")
+    p.add_argument("--lars-eta", type=float, default=1e-3,
+                   help="lars: trust coefficient")
+    p.add_argument("--max-grad-norm", type=float, default=0.0,
+                   help="lars: clip the global gradient norm (0 = off)")
+    p.add_argument("--lr-schedule", choices=["none", "warmup-poly"],
+                   default="none",
+                   help="warmup-poly: linear ramp 0 -> --lr over "
+                        "--warmup-steps, then (1 - t)^2 decay to 0 at --steps")
+    p.add_argument("--warmup-steps", type=int, default=0)
     p.add_argument("--data", default="synthetic",
                    help="'synthetic' or a dataset name/path (ILSVRC layout)")
     p.add_argument("--nsamples", type=int, default=None,
@@ -83,8 +97,31 @@ def parse_args():
 def make_opt_factory(args):
     if args.optimizer == "adam":
         return lambda m: FusedAdam(m.parameters(), lr=args.lr)
+    if args.optimizer == "lars":
+        return lambda m: FusedLARS(
+            m.parameters(), lr=args.lr, momentum=args.momentum,
+            weight_decay=args.weight_decay, eta=args.lars_eta,
+            max_grad_norm=args.max_grad_norm)
     return lambda m: FusedSGDMomentum(m.parameters(), lr=args.lr,
                                       momentum=args.momentum)
+
+
+def make_sched(args, optimizers, done=0):
+    """--lr-schedule as a `sched(cycle)` over all of `optimizers` (one per
+    replica), already applied for cycle `done`; None for 'none'."""
+    if args.lr_schedule == "none":
+        return None
+    from fluxdistributed_amd.utils.schedule import warmup_poly
+
+    scheds = [warmup_poly(o, args.lr, args.warmup_steps, args.steps)
+              for o in optimizers]
+
+    def sched(cycle):
+        for s in scheds:
+            s(cycle)
+
+    sched(done)
+    return sched
 
 
 def make_batch_fn(args, rank=0, world=1):
@@ -176,6 +213,7 @@ def run_task(args):
             )
 
     results = train(logit_cross_entropy, st, steps=args.steps,
+                    sched=make_sched(args, [r.optimizer for r in st.replicas]),
                     log_every=args.log_every, val_every=args.val_every,
                     on_cycle_end=on_cycle_end, fused_eval=args.fused_eval)
     log.info("done: %d cycles, %d missed; timers=%s", st.cycles, st.num_missed,
@@ -208,6 +246,8 @@ def run_process(args):
         model, opt, logit_cross_entropy, loader, steps=args.steps,
         checkpoint_every=args.checkpoint_every,
         checkpoint_dir=args.checkpoint_dir, fused_eval=args.fused_eval,
+        sched=make_sched(args, [opt]),
+        log_every=args.log_every if args.optimizer == "lars" else 0,
     )
     if rank == 0:
         log.info("done: %s", stats)
