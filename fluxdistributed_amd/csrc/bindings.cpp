@@ -986,6 +986,33 @@ std::tuple<int64_t, int64_t, int64_t, bool> conv_igemm_fwd_config(
     return {plan.bm, plan.bn, plan.sk, plan.ring};
 }
 
+// The plan a body wgrad with M = N*P*Q pixels runs: (FT, mch, nch, nwg),
+// from the plan the launcher itself obeys.
+std::tuple<int64_t, int64_t, int64_t, int64_t> conv_igemm_wgrad_config(
+    int64_t M, int64_t C, int64_t K, int64_t R, int64_t S) {
+    TORCH_CHECK(M >= 1 && M <= INT32_MAX && C >= 64 && C % 64 == 0 &&
+                    K >= 64 && K % 64 == 0 && R >= 1 && S >= 1,
+                "conv_igemm_wgrad_config: bad geometry");
+    const auto p = fda::conv_wgrad_plan(M, (int)C, (int)K, (int)R, (int)S);
+    return {p.ft, p.mch, p.nch, p.nwg};
+}
+
+// The (ktile, ctile, rs, chunk) that block `bid` of a wgrad grid of
+// ktiles*ctiles*RS*nch blocks owns, by the decode the kernel runs. The stem
+// grid is ctiles = 1, RS = R.
+std::tuple<int64_t, int64_t, int64_t, int64_t> conv_wgrad_block_coords(
+    int64_t bid, int64_t ktiles, int64_t ctiles, int64_t RS, int64_t nch) {
+    TORCH_CHECK(ktiles >= 1 && ctiles >= 1 && RS >= 1 && nch >= 1 &&
+                    ktiles * ctiles * RS * nch <= INT32_MAX,
+                "conv_wgrad_block_coords: bad grid");
+    TORCH_CHECK(bid >= 0 && bid < ktiles * ctiles * RS * nch,
+                "conv_wgrad_block_coords: bid ", bid, " outside the grid of ",
+                ktiles * ctiles * RS * nch, " blocks");
+    const auto c = fda::wgrad_block_coords((unsigned)bid, (int)ktiles,
+                                           (int)ctiles, (int)RS, (int)nch);
+    return {c.ktile, c.ctile, c.rs, c.chunk};
+}
+
 // ---- inference forward: conv + eval BN + residual + ReLU in one kernel ----
 
 // y = bf16(relu(scale[k] * conv(x, w) + shift[k] + residual)), rounded once
@@ -1357,6 +1384,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("max_c"),
           "eval-mode BN scale/shift of every layer in one launch");
     m.def("conv_igemm_wgrad_into", &conv_igemm_wgrad_into);
+    m.def("conv_igemm_wgrad_config", &conv_igemm_wgrad_config,
+          "The (FT, mch, nch, nwg) plan a body wgrad with M pixels runs");
+    m.def("conv_wgrad_block_coords", &conv_wgrad_block_coords,
+          "Block id -> (ktile, ctile, rs, chunk) of a wgrad grid");
     m.def("conv_igemm_wgrad", &conv_igemm_wgrad,
           "implicit-GEMM conv weight-grad (NHWC bf16, MFMA + tr16 reads)");
     m.def("conv_igemm_dgrad", &conv_igemm_dgrad,

@@ -58,7 +58,12 @@
 // transpose reads from an m4-grouped LDS image, window positions
 // permuted for bank-conflict-free half-wave reads, fp32 atomic chunk
 // accumulation), and the batched weight transposer for the dgrad B
-// layout.
+// layout. The wgrad grid is 1-D: a block id maps through an XCD-contiguous
+// logical id, pixel chunk slowest, to (k-tile, c-tile, tap, chunk)
+// (wgrad_block_coords, fda_kernels.h), so the blocks that stage one
+// chunk's dy and x tiles run back to back behind one XCD's L2; and
+// conv_wgrad_plan sizes the chunks so the grid is one resident wave of
+// blocks (profiles/wgrad_raster.md).
 //
 // Constraints (host wrapper): staged reduction channels (C fwd / K dgrad)
 // and output channels multiples of 64, dilation 1, groups 1; everything
@@ -904,10 +909,11 @@ typedef __attribute__((ext_vector_type(4))) short short4_;
 // Each block owns a (32*FT)k x (32*FT)c output tile (FT = fragments per
 // wave axis: 2 -> 64x64 tile / 8 MFMAs per K-step, 4 -> 128x128 tile /
 // 32 MFMAs — chosen by channel divisibility; the bigger tile quadruples
-// the MFMA-per-glds ratio) for one (r,s) tap and a 2048-pixel M-chunk;
-// chunks accumulate into an fp32 workspace with atomicAdd.
+// the MFMA-per-glds ratio) for one (r,s) tap and one M-chunk of pixels
+// (conv_wgrad_plan sizes it; the stem uses 8 * WG_MCH); chunks accumulate
+// into an fp32 workspace with atomicAdd.
 constexpr int WG_BM = 64;      // m per K-step
-constexpr int WG_MCH = 2048;   // pixels per block (chunk)
+constexpr int WG_MCH = 2048;   // chunk of small problems, the stem's unit
 
 template <int FT, bool STEM = false>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(
@@ -923,11 +929,17 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(
     constexpr int GI = MB * TCH / 2048;      // glds per wave per operand
     constexpr int NWIN = MB / 4;             // tr16 windows (4 m x 16 ch)
     constexpr int KSN = MB / 32;             // MFMA m-halves per K-step
-    const int rs = blockIdx.z / nch;
-    const int chunk = blockIdx.z % nch;
+    // 1-D grid, chunk-major and XCD-contiguous: the blocks of one pixel
+    // chunk (every tap, every tile pair) stage the same dy bytes and nearly
+    // the same x bytes, so they get adjacent logical ids and with them one
+    // XCD's L2 (wgrad_block_coords, fda_kernels.h).
+    const WgradCoords bc = wgrad_block_coords(blockIdx.x, K / TCH, C / TCH,
+                                              R * S, nch);
+    const int rs = bc.rs;
+    const int chunk = bc.chunk;
     const int r = rs / S, s = rs % S;
-    const int k0 = blockIdx.x * TCH;
-    const int c0 = blockIdx.y * TCH;
+    const int k0 = bc.ktile * TCH;
+    const int c0 = bc.ctile * TCH;
     const long M = (long)N * P * Q;
     const long mb0 = (long)chunk * mch;
     const long mend = (mb0 + mch < M) ? mb0 + mch : M;
@@ -1128,7 +1140,8 @@ void conv_stem_wgrad_launch(const void* dy, const void* x, float* ws,
     const long M = g.rows(CONV_STEM);
     constexpr int STEM_MCH = 8 * WG_MCH;    // 16k pixels: balances atomic fan-in per address against block count (32k measured 472 us/step vs 254 at 16k)
     const int nch = (int)((M + STEM_MCH - 1) / STEM_MCH);
-    dim3 grid((unsigned)(g.K / 64), 1u, (unsigned)(g.R * nch));
+    // block order (chunk, r, ktile): the seven r taps of a chunk share dy
+    const dim3 grid((unsigned)((g.K / 64) * g.R * nch));
     const size_t shmem = 3 * 2 * (WG_BM * 64) * sizeof(unsigned short);
     hipLaunchKernelGGL((conv_wgrad_kernel<2, true>), grid, dim3(256), shmem,
                        stream, (const unsigned short*)dy,
@@ -1136,54 +1149,66 @@ void conv_stem_wgrad_launch(const void* dy, const void* x, float* ws,
                        g.P, g.Q, g.R, 1, g.sy, g.sx, 0, 0, nch, STEM_MCH);
 }
 
-// pick the pixel-chunk size so the grid lands near `target` blocks:
-// enough parallelism to fill the chip, few enough chunks that the fp32
-// atomic fan-in per output address stays small.
-static int pick_mch(long M, long tiles, int target) {
-    long nch_t = target / (tiles > 0 ? tiles : 1);
-    if (nch_t < 1) nch_t = 1;
-    long mch = (M + nch_t - 1) / nch_t;
-    mch = ((mch + WG_MCH - 1) / WG_MCH) * WG_MCH;   // multiple of 2048
-    if (mch < WG_MCH) mch = WG_MCH;
-    return (int)mch;
-}
+// Chunk plan. The grid is sized to ONE resident wave of blocks: 256 CUs x 2
+// blocks (FT4: 64 KiB LDS, 176 VGPRs) or x 3 (FT2: 48 KiB LDS), and never
+// more, since a few blocks past the resident slots run as a second wave
+// behind the first (792 blocks on 768 slots measured 47 us where 720 take
+// 39). More chunks mean more fp32 atomics (K*RS*C*4 bytes per chunk at about
+// 1.3 TB/s chip-wide), which is what keeps the count from going higher:
+// twice the slots measured slower on every shape. A 1x1 filter has no taps
+// that share operand tiles and its atomic epilogue weighs more against its
+// short K-loop, so it takes half the slots (12.4 us against 13.5 at all of
+// them and 24.5 at the old 2048-pixel chunks). Chunks are whole 64-pixel
+// K-steps, of even length (4704 pixels in 3 chunks are 1600+1600+1504, not
+// 2048+2048+608), and no shorter than the shortest measured, 7 K-steps.
+// profiles/wgrad_raster.md has the candidates per shape.
+// Up to 2 * WG_MCH pixels the plan stays at one or two WG_MCH chunks: with
+// at most two addends per address the fp32 sum does not depend on the
+// order the atomics arrive in, so small problems keep giving the same bits
+// from run to run (the small-model DDP tests compare runs bit for bit),
+// and nothing was measured there.
+constexpr int WG_CUS = 256;
+constexpr int WG_MIN_MCH = 7 * WG_BM;
 
-// tile/chunk plan: FT (fragments per wave axis), pixels per chunk, chunks
-static void conv_wgrad_plan(long M, int C, int K, int R, int S,
-                            int* ft, int* mch, int* nch) {
+// tile/chunk plan: FT (fragments per wave axis), pixels per chunk, chunks,
+// and the 1-D grid (tile pairs x taps x chunks)
+WgradPlan conv_wgrad_plan(long M, int C, int K, int R, int S) {
+    WgradPlan p;
     // FT=4 quarters the block count; only worth it when the grid still
     // fills the 256 CUs (small-M 1x1 shapes measured 1.4x slower on it)
     const long tiles4 = (long)(K / 128) * (C / 128) * R * S;
+    const long tiles2 = (long)(K / 64) * (C / 64) * R * S;
     const long blocks4_max = tiles4 * ((M + WG_MCH - 1) / WG_MCH);
-    if (K % 128 == 0 && C % 128 == 0 && blocks4_max >= 192) {
-        *ft = 4;
-        *mch = pick_mch(M, tiles4, 768);
-    } else {
-        *ft = 2;
-        *mch = pick_mch(M, (long)(K / 64) * (C / 64) * R * S, 768);
-    }
-    *nch = (int)((M + *mch - 1) / *mch);
+    p.ft = (K % 128 == 0 && C % 128 == 0 && blocks4_max >= 192) ? 4 : 2;
+    const long tiles = p.ft == 4 ? tiles4 : tiles2;
+    const long slots = WG_CUS * (p.ft == 4 ? 2 : 3);
+    long nch = (R * S == 1 ? slots / 2 : slots) / tiles;
+    if (nch < 1) nch = 1;
+    long mch = ((M + nch - 1) / nch + WG_BM - 1) / WG_BM * WG_BM;
+    if (mch < WG_MIN_MCH) mch = WG_MIN_MCH;
+    if (M <= 2 * WG_MCH) mch = WG_MCH;
+    p.mch = (int)mch;
+    p.nch = (int)((M + mch - 1) / mch);
+    p.nwg = tiles * p.nch;
+    return p;
 }
 
 void conv_wgrad_launch(const void* dy, const void* x, float* ws,
                        const ConvGeom& g, hipStream_t stream) {
-    int FTp, mch, nch;
-    conv_wgrad_plan(g.rows(CONV_FWD), g.C, g.K, g.R, g.S, &FTp, &mch, &nch);
+    const WgradPlan p = conv_wgrad_plan(g.rows(CONV_FWD), g.C, g.K, g.R, g.S);
     // one argument list for both tile sizes
-    auto launch = [&](auto kern, int tch, size_t shmem) {
-        dim3 grid((unsigned)(g.K / tch), (unsigned)(g.C / tch),
-                  (unsigned)(g.R * g.S * nch));
-        hipLaunchKernelGGL(kern, grid, dim3(256), shmem, stream,
-                           (const unsigned short*)dy,
+    auto launch = [&](auto kern, size_t shmem) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)p.nwg), dim3(256), shmem,
+                           stream, (const unsigned short*)dy,
                            (const unsigned short*)x, ws, g.N, g.H, g.W, g.C,
                            g.K, g.P, g.Q, g.R, g.S, g.sy, g.sx, g.py, g.px,
-                           nch, mch);
+                           p.nch, p.mch);
     };
-    if (FTp == 4)
-        launch(conv_wgrad_kernel<4>, 128,
+    if (p.ft == 4)
+        launch(conv_wgrad_kernel<4>,
                2 * 2 * (WG_BM * 128) * sizeof(unsigned short));
     else
-        launch(conv_wgrad_kernel<2>, 64,
+        launch(conv_wgrad_kernel<2>,
                3 * 2 * (WG_BM * 64) * sizeof(unsigned short));
 }
 

@@ -111,15 +111,8 @@ __device__ __forceinline__ bool bn_relu_positive(float x, float scale,
     return load_f32(&t) > 0.f;
 }
 
-// XCD-aware block remap (bijective for any grid size): blocks that share
-// `blockIdx % 8` share an L2, so give each such group a contiguous range
-// of logical ids. A pure locality choice — any mapping is correct.
-__device__ __forceinline__ unsigned xcd_contiguous_block(unsigned bid,
-                                                         unsigned nwg) {
-    const unsigned q = nwg / 8, r = nwg % 8, xcd = bid % 8;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + bid / 8;
-}
+// xcd_contiguous_block (the XCD-aware block remap) lives in fda_kernels.h:
+// the bindings decode block ids with it on the host.
 
 // ---- wave / block reductions ----------------------------------------------
 __device__ __forceinline__ float wave_reduce_sum(float v) {

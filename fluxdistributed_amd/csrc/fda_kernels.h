@@ -225,6 +225,48 @@ void conv_stem_fwd_launch(const void* src, const void* wgt, void* out,
 void conv_stem_wgrad_launch(const void* dy, const void* x, float* ws,
                             const ConvGeom& g, hipStream_t stream);
 
+// XCD-aware block remap (bijective for any grid size): blocks that share
+// `blockIdx % 8` share an L2, so give each such group a contiguous range
+// of logical ids. A pure locality choice — any mapping is correct.
+__host__ __device__ __forceinline__ unsigned xcd_contiguous_block(
+    unsigned bid, unsigned nwg) {
+    const unsigned q = nwg / 8, r = nwg % 8, xcd = bid % 8;
+    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+    return base + bid / 8;
+}
+
+// What a wgrad of M = N*P*Q pixels runs: FT fragments per wave axis (a
+// (32*FT)k x (32*FT)c output tile per block), mch pixels per chunk (whole
+// 64-pixel K-steps), nch chunks, and the 1-D grid of nwg =
+// (K/tile)*(C/tile)*R*S*nch blocks. The launcher obeys it.
+struct WgradPlan {
+    int ft, mch, nch;
+    long nwg;
+};
+WgradPlan conv_wgrad_plan(long M, int C, int K, int R, int S);
+
+// Which (k-tile, c-tile, filter tap, pixel chunk) block `bid` of a wgrad
+// grid owns. The logical id is XCD-contiguous and decoded chunk slowest,
+//   L = ((chunk*RS + rs)*ctiles + ctile)*ktiles + ktile,
+// so all blocks of a chunk, which stage the same dy tile and (for a 3x3
+// filter) nearly the same x bytes, run back to back behind one L2. The stem
+// is the case ctiles = 1, RS = R. One function for the kernel and for the
+// binding that lets a test enumerate the grid.
+struct WgradCoords {
+    int ktile, ctile, rs, chunk;
+};
+__host__ __device__ __forceinline__ WgradCoords wgrad_block_coords(
+    unsigned bid, int ktiles, int ctiles, int RS, int nch) {
+    const unsigned nwg = (unsigned)(ktiles * ctiles * RS * nch);
+    unsigned L = xcd_contiguous_block(bid, nwg);
+    WgradCoords c;
+    c.ktile = (int)(L % (unsigned)ktiles); L /= (unsigned)ktiles;
+    c.ctile = (int)(L % (unsigned)ctiles); L /= (unsigned)ctiles;
+    c.rs = (int)(L % (unsigned)RS);
+    c.chunk = (int)(L / (unsigned)RS);
+    return c;
+}
+
 // wgrad: ws[K][RS*C] fp32 (pre-zeroed) += dy^T @ im2col(x), atomic chunks.
 void conv_wgrad_launch(const void* dy, const void* x, float* ws,
                        const ConvGeom& g, hipStream_t stream);

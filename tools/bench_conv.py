@@ -5,6 +5,7 @@ Times fwd and dgrad for every ResNet-34 bs-96 body shape; prints a table
 with effective TFLOP/s. Run on a GPU box:
     python tools/bench_conv.py [--batch 96] [--iters 50]
     python tools/bench_conv.py --mode dgrad --iters 200   # dgrad arms only
+    python tools/bench_conv.py --mode wgrad --iters 200   # wgrad arms only
 """
 
 import argparse
@@ -100,15 +101,57 @@ def dgrad_arms(args):
     print(f"{'TOTAL (weighted by layer count)':34s} {tot[0]:22.1f} {tot[1]:22.1f}")
 
 
+def wgrad_arms(args):
+    """Weight-grad arms: the kernel alone, accumulating into one workspace
+    (conv_igemm_wgrad_into, as the train step calls it), and with the
+    workspace allocation and zero fill (conv_igemm_wgrad). Figures as for
+    --mode dgrad: the median of --repeats timed blocks and their min..max."""
+    C_ = require_native("conv_igemm_wgrad_into")
+    n = args.batch
+    print(f"# batch={n} wgrad, us per call: median (min..max) of "
+          f"{args.repeats} blocks of {args.iters} calls")
+    print(f"{'shape':34s} {'kernel (into)':>22s} {'with zero fill':>22s}")
+    shapes = SHAPES if args.only < 0 else [SHAPES[args.only]]
+    tot = [0.0, 0.0]
+    for (c, h, w, k, r, s, cnt) in shapes:
+        pad = r // 2
+        P, Q = (h + 2 * pad - r) // s + 1, (w + 2 * pad - r) // s + 1
+        gy = torch.randn(n, k, P, Q, device="cuda").bfloat16() \
+            .contiguous(memory_format=torch.channels_last)
+        x = torch.randn(n, c, h, w, device="cuda").bfloat16() \
+            .contiguous(memory_format=torch.channels_last)
+        ws = torch.zeros(k * r * r * c, device="cuda")
+        arms = [
+            lambda: C_.conv_igemm_wgrad_into(gy, x, ws, r, r, s, s, pad, pad),
+            lambda: C_.conv_igemm_wgrad(gy, x, r, r, s, s, pad, pad),
+        ]
+        cells = []
+        # blocks of the arms in turn, so drift hits every arm alike
+        ts = [[] for _ in arms]
+        for _ in range(args.repeats):
+            for i, fn in enumerate(arms):
+                ts[i].append(event_us(fn, args.iters))
+        for i, t in enumerate(ts):
+            t.sort()
+            med = t[len(t) // 2]
+            tot[i] += med * cnt
+            cells.append(f"{med:7.1f} ({t[0]:.1f}..{t[-1]:.1f})")
+        name = f"{c}x{h}x{w} k{k} {r}x{r} s{s} x{cnt}"
+        print(f"{name:34s} {cells[0]:>22s} {cells[1]:>22s}")
+    print(f"{'TOTAL (weighted by layer count)':34s} {tot[0]:22.1f} {tot[1]:22.1f}")
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, default=96)
     p.add_argument("--iters", type=int, default=50)
     p.add_argument("--repeats", type=int, default=5,
-                   help="timed blocks per arm (--mode dgrad)")
-    p.add_argument("--mode", choices=["fwd", "dgrad", "both"], default="both",
+                   help="timed blocks per arm (--mode dgrad, wgrad)")
+    p.add_argument("--mode", choices=["fwd", "dgrad", "wgrad", "both"],
+                   default="both",
                    help="dgrad: only the input-grad arms, plain and with "
-                        "accum, with their run-to-run spread")
+                        "accum, with their run-to-run spread; wgrad: only "
+                        "the weight-grad arms, likewise")
     p.add_argument("--only", type=int, default=-1,
                    help="run only SHAPES[i] (for PMC profiling runs)")
     p.add_argument("--fda-only", action="store_true",
@@ -117,6 +160,8 @@ def main():
     assert torch.cuda.is_available()
     if args.mode == "dgrad":
         return dgrad_arms(args)
+    if args.mode == "wgrad":
+        return wgrad_arms(args)
     torch.backends.cudnn.benchmark = True
     C_ = require_native("conv_igemm_fwd")
     n = args.batch
