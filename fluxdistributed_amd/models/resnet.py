@@ -15,6 +15,7 @@ from typing import List, Optional, Tuple, Type
 import torch
 import torch.nn as nn
 
+from ..ops.conv import FdaConv2d, _native_supported
 from ..ops.linear import FdaLinear
 from ..ops.functional import (batch_norm_act, batch_norm_act_pool,
                               bn_act_pool_fusible, MaxPool2d, GlobalAvgPool)
@@ -86,11 +87,7 @@ def _junction_fusible(x: torch.Tensor, conv: nn.Conv2d) -> bool:
     `conv`'s native dgrad += epilogue: the SAME tensor x must reach the
     native dgrad (channels_last, native-supported shape) and need a grad.
     The contract is load-bearing — a deferred gres that no dgrad consumes
-    raises in ops/conv.py rather than silently dropping gradient."""
-    import os
-
-    from ..ops.conv import _native_supported
-
+    raises in ops/step_state.py rather than silently dropping gradient."""
     if os.environ.get("FLUXDIST_JUNCTION", "1") == "0":
         return False
     if not (torch.is_grad_enabled() and x.requires_grad):
@@ -102,14 +99,10 @@ def _junction_fusible(x: torch.Tensor, conv: nn.Conv2d) -> bool:
 
 
 def conv3x3(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
-    from ..ops.conv import FdaConv2d
-
     return FdaConv2d(cin, cout, 3, stride=stride, padding=1, bias=False)
 
 
 def conv1x1(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
-    from ..ops.conv import FdaConv2d
-
     return FdaConv2d(cin, cout, 1, stride=stride, bias=False)
 
 
@@ -182,8 +175,6 @@ class ResNet(nn.Module):
         super().__init__()
         self.small_input = small_input
         self.cin = 64
-        from ..ops.conv import FdaConv2d
-
         if small_input:  # CIFAR-style stem (BASELINE config 1)
             self.conv1 = FdaConv2d(3, 64, 3, stride=1, padding=1, bias=False)
             self.maxpool = nn.Identity()

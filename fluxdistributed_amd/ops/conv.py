@@ -16,13 +16,19 @@ Env:
 """
 
 import os
-import threading
 from typing import Tuple
 
 import torch
 import torch.nn.functional as F
 
+from .arenas import stem_pool_get, stem_pool_put, wgrad_arena, wt_arena
+from .gradflush import queue_or_flush
 from .native import load_native, require_native
+from .step_state import (clear_conv_stats, flat_grad_slice, stash_conv_stats,
+                         take_junction_gres)
+# names that callers outside ops/ import from here
+from .step_state import bump_step_epoch as bump_conv_wt_marker  # noqa: F401
+from .step_state import junction_stash_empty  # noqa: F401
 
 
 def _pair(v) -> Tuple[int, int]:
@@ -43,221 +49,6 @@ def _native_supported(x: torch.Tensor, w: torch.Tensor, stride, padding,
     return load_native() is not None
 
 
-class _WtArena:
-    """Per-device cache of transposed conv weights wt[rs*C+c][k] for dgrad.
-
-    All registered weights are transposed in ONE kernel launch per training
-    step (wt_transpose_batch) instead of 36 per-layer permutes. Freshness:
-    a marker bumped by the fused optimizers (ops/fused_optim.py write params
-    through raw kernels, invisible to autograd) plus the sum of the weights'
-    `_version` counters (covers torch.optim in-place updates).
-    """
-
-    def __init__(self, device):
-        self.device = device
-        self.weights = []               # [(weight, K, RC)]
-        self.slices = {}                # id(weight) -> (offset, RC, K)
-        self.arena = None
-        self.meta = None
-        self.fresh_key = None
-        # arenas are shared per-device across task-DDP replica threads:
-        # register/rebuild/refresh are check-then-act and must not interleave
-        self.lock = threading.Lock()
-
-    def register(self, weight):
-        with self.lock:
-            if id(weight) in self.slices:
-                return
-            K, Cin, R, S = weight.shape
-            RC = R * S * Cin
-            self.weights.append((weight, K, RC))
-            self.slices[id(weight)] = (None, RC, K)
-            self.arena = None           # rebuild on next get
-
-    def _build(self):
-        dev = self.device
-        total = sum(K * RC for (_, K, RC) in self.weights)
-        self.arena = torch.empty(total, dtype=torch.bfloat16, device=dev)
-        off = 0
-        srcs, dsts, Ks, RCs, tiles = [], [], [], [], []
-        for (w, K, RC) in self.weights:
-            self.slices[id(w)] = (off, RC, K)
-            srcs.append(w.data_ptr())
-            dsts.append(self.arena.data_ptr() + off * 2)
-            Ks.append(K)
-            RCs.append(RC)
-            tiles.append((K // 64) * (RC // 64))
-            off += K * RC
-        self.src_ptrs = srcs
-        mk = lambda v, dt: torch.tensor(v, dtype=dt, device=dev)
-        self.meta = (mk(srcs, torch.long), mk(dsts, torch.long),
-                     mk(Ks, torch.int32), mk(RCs, torch.int32),
-                     mk(tiles, torch.int32), max(tiles))
-
-    def get(self, weight):
-        with self.lock:
-            key = (_WT_MARKER[0], sum(w._version for (w, _, _) in self.weights))
-            if self.arena is None:
-                self._build()
-                self.fresh_key = None
-            if self.fresh_key != key:
-                # Revalidate source pointers before re-transposing: a p.data
-                # rebind (flat-optimizer construction after a warmup backward,
-                # model.to(), checkpoint load) leaves the baked device-side
-                # meta pointing at freed storage. Checked only on refresh
-                # (once per step), not per get().
-                if [w.data_ptr() for (w, _, _) in self.weights] != self.src_ptrs:
-                    self._build()
-                C = require_native("wt_transpose_batch")
-                s, d, k, rc, t, mt = self.meta
-                C.wt_transpose_batch(s, d, k, rc, t, mt)
-                self.fresh_key = key
-            off, RC, K = self.slices[id(weight)]
-            return self.arena[off : off + RC * K].view(RC, K)
-
-
-class _WgradArena:
-    """Step-scoped fp32 wgrad workspace: zeroed in ONE launch per backward
-    epoch instead of a per-layer `zeros` each (the wgrad kernel accumulates
-    into its slice with atomicAdd). A second wgrad call for the same weight
-    inside one epoch (gradient micro-accumulation) re-zeros just its slice
-    so the returned dw stays the per-backward gradient."""
-
-    def __init__(self, device):
-        self.device = device
-        self.slices = {}               # id(weight) -> (offset, numel, wref)
-        self.sizes = []
-        self.arena = None
-        self.zero_epoch = None
-        self.seen = set()
-        # shared per-device across replica threads; without the lock two
-        # threads can BOTH see zero_epoch stale and the second whole-arena
-        # zero_() lands after the first thread's wgrad kernel (silent wipe)
-        self.lock = threading.Lock()
-
-    def get(self, weight):
-        import weakref
-
-        with self.lock:
-            K, Cin, R, S = weight.shape
-            n = K * Cin * R * S
-            ent = self.slices.get(id(weight))
-            if ent is not None and ent[2]() is not weight:
-                ent = None          # CPython recycled a dead weight's id
-            if ent is None:
-                self.slices[id(weight)] = (sum(self.sizes), n,
-                                           weakref.ref(weight))
-                self.sizes.append(n)
-                self.arena = None
-            if self.arena is None:
-                total = sum(self.sizes)
-                self.arena = torch.empty(total, dtype=torch.float32,
-                                         device=self.device)
-                self.zero_epoch = None
-            epoch = _WT_MARKER[0]
-            off, n, _ = self.slices[id(weight)]
-            sl = self.arena[off : off + n]
-            if self.zero_epoch != epoch:
-                self.arena.zero_()
-                self.zero_epoch = epoch
-                self.seen = set()
-            elif id(weight) in self.seen:
-                sl.zero_()
-            self.seen.add(id(weight))
-            return sl.view(K, R * S * Cin)
-
-
-_WT_MARKER = [0]
-_ARENAS: dict = {}
-_WS_ARENAS: dict = {}
-
-# Free-list pool of padded stem inputs, keyed by shape. A buffer is checked
-# OUT at stem forward (exclusively owned by that autograd graph via ctx.x8)
-# and returned at backward — so concurrent task-DDP replica threads,
-# gradient micro-accumulation, or two same-shape stems each get their own
-# buffer and wgrad always reads the input of ITS forward. Pool reuse keeps
-# the zero border: only the interior is rewritten on checkout.
-_STEM_POOL: dict = {}
-_STEM_POOL_LOCK = threading.Lock()
-_STEM_POOL_CAP = 8   # per shape; beyond this, dropped buffers are GC'd
-
-
-def _stem_pool_get(key):
-    with _STEM_POOL_LOCK:
-        lst = _STEM_POOL.get(key)
-        if lst:
-            return lst.pop()
-    return None
-
-
-def _stem_pool_put(key, buf):
-    with _STEM_POOL_LOCK:
-        lst = _STEM_POOL.setdefault(key, [])
-        if len(lst) < _STEM_POOL_CAP:
-            lst.append(buf)
-
-
-# Per-thread single-slot handshake: the conv fwd epilogue accumulates
-# per-channel sum/sumsq of its (rounded) output; the immediately following
-# BatchNorm on the SAME thread consumes them and skips its own stats read
-# pass. Thread-local so task-DDP replica threads can't cross-feed; cleared
-# at every conv forward so an unconsumed stash can't later match a
-# recycled allocator pointer of the same shape.
-_TLS = threading.local()
-
-
-def stash_conv_stats(y, part):
-    _TLS.conv_stats = (y.data_ptr(), tuple(y.shape), part)
-
-
-# Residual-junction grad stash: at an identity-shortcut junction the grad
-# wrt x is dgrad(conv1) + gres(BN residual). When the block knows conv1's
-# dgrad will run on the native kernel (models/resnet.py), the BN backward
-# DEFERS gres here (returning None to autograd) and the conv dgrad folds
-# it in via the kernel's += epilogue — autograd's separate
-# CUDAFunctor_add pass over the full activation disappears.
-# Thread-local (task-DDP replica threads), keyed by (data_ptr, shape) of
-# the junction tensor; entries MUST be consumed by the very next dgrad of
-# that tensor (backward visits bn2 ... conv1 strictly in order on the
-# identity path), and an unconsumed entry is a loud error, never a silent
-# gradient drop.
-
-
-def stash_junction_gres(key, gres):
-    d = getattr(_TLS, "junction", None)
-    if d is None:
-        d = _TLS.junction = {}
-    if key in d:
-        raise RuntimeError(
-            "residual-junction gres stash collision: previous deferred "
-            "gradient was never consumed by a conv dgrad (fusion contract "
-            "broken — check models/resnet.py _junction_fusible gating)")
-    d[key] = gres
-
-
-def take_junction_gres(x):
-    d = getattr(_TLS, "junction", None)
-    if not d:
-        return None
-    return d.pop((x.data_ptr(), tuple(x.shape)), None)
-
-
-def junction_stash_empty() -> bool:
-    return not getattr(_TLS, "junction", None)
-
-
-def clear_conv_stats():
-    _TLS.conv_stats = None
-
-
-def take_conv_stats(x):
-    ent = getattr(_TLS, "conv_stats", None)
-    _TLS.conv_stats = None
-    if ent is not None and ent[0] == x.data_ptr() and ent[1] == tuple(x.shape):
-        return ent[2]
-    return None
-
-
 def _want_conv_stats() -> bool:
     """Decided in the DISPATCHER (fda_conv2d), where grad mode is visible —
     inside Function.forward torch.is_grad_enabled() is always False, which
@@ -265,19 +56,6 @@ def _want_conv_stats() -> bool:
     their own stats pass despite the handshake)."""
     return (torch.is_grad_enabled()
             and os.environ.get("FLUXDIST_BN_FUSE", "1") != "0")
-
-
-def bump_conv_wt_marker():
-    """Invalidate cached transposed weights. Called by the fused optimizers
-    after each raw-kernel parameter update."""
-    _WT_MARKER[0] += 1
-
-
-def _arena_for(weight) -> _WtArena:
-    dev = weight.device
-    if dev not in _ARENAS:
-        _ARENAS[dev] = _WtArena(dev)
-    return _ARENAS[dev]
 
 
 class _FdaConv2d(torch.autograd.Function):
@@ -303,7 +81,7 @@ class _FdaConv2d(torch.autograd.Function):
         ctx.save_for_backward(xc, wc)
         ctx.conf = (stride, padding, weight is wc)
         if weight is wc:  # already channels_last: cacheable by identity
-            _arena_for(wc).register(wc)
+            wt_arena(wc.device).register(wc)
         return y
 
     @staticmethod
@@ -318,7 +96,7 @@ class _FdaConv2d(torch.autograd.Function):
             C = require_native("conv_igemm_dgrad")
             K, Cin, R, S = w.shape
             if cacheable:
-                wt = _arena_for(w).get(w)
+                wt = wt_arena(w.device).get(w)
             else:
                 # wt[(r*S+s)*C + c][k]: k-contiguous rows for the B tile
                 wt = w.permute(2, 3, 1, 0).reshape(R * S * Cin, K).contiguous()
@@ -330,15 +108,10 @@ class _FdaConv2d(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             K, Cin, R, S = w.shape
             if os.environ.get("FLUXDIST_WGRAD", "") != "miopen":
-                from .fused_optim import flat_grad_slice
-
                 C = require_native("conv_igemm_wgrad")
                 g_sl = flat_grad_slice(w) if cacheable else None
                 if cacheable:
-                    dev = w.device
-                    if dev not in _WS_ARENAS:
-                        _WS_ARENAS[dev] = _WgradArena(dev)
-                    ws = _WS_ARENAS[dev].get(w)
+                    ws = wgrad_arena(w.device).get(w)
                     C.conv_igemm_wgrad_into(gy, x, ws, R, S, sy, sx, py, px)
                 else:
                     ws = C.conv_igemm_wgrad(gy, x, R, S, sy, sx, py, px)
@@ -347,8 +120,6 @@ class _FdaConv2d(torch.autograd.Function):
                     # ([K][R][S][C]); one fused cast+add, no AccumulateGrad.
                     # Queued + batched at backward end unless a DDP
                     # bucketer needs it immediately (ops/gradflush.py).
-                    from .gradflush import queue_or_flush
-
                     queue_or_flush(w, g_sl, ws.reshape(-1))
                     dw = None
                 else:
@@ -413,7 +184,7 @@ class _FdaStemConv2d(torch.autograd.Function):
         # forwards — round-1 ADVICE #1).
         key = stem_buffer_key(x, weight, padding)
         x8, wpad, P, Q = pack_stem_operands(xc, weight, stride, padding,
-                                            _stem_pool_get(key))
+                                            stem_pool_get(key))
         if want_stats:
             y, part = C.conv_stem_fwd_stats(x8, wpad, R, sy, sx, P, Q)
             stash_conv_stats(y, part)
@@ -435,7 +206,7 @@ class _FdaStemConv2d(torch.autograd.Function):
             # this buffer; return it now. Stream-ordered reuse on the same
             # stream is safe.
             ctx.x8 = None
-            _stem_pool_put(key, x8)
+            stem_pool_put(key, x8)
         ctx.conf = (K, Cin, R, S, sy, sx)
         return y
 
@@ -457,7 +228,7 @@ class _FdaStemConv2d(torch.autograd.Function):
             dw = (ws.view(K, R, 8, 8)[:, :, :S, :Cin]
                   .to(torch.bfloat16).permute(0, 3, 1, 2))
         ctx.x8 = None
-        _stem_pool_put(ctx.pool_key, x8)
+        stem_pool_put(ctx.pool_key, x8)
         return None, dw, None, None, None
 
 

@@ -14,6 +14,8 @@ import torch
 import torch.nn.functional as F
 
 from .native import require_native
+from .step_state import (flat_grad_slice, notify_grad_written,
+                         stash_junction_gres, take_conv_stats)
 
 
 def _on_gpu(*tensors) -> bool:
@@ -141,10 +143,8 @@ class MaxPool2d(torch.nn.Module):
 def _direct_grad_slices(weight, bias):
     """Direct grads: when both BN params live in a fused-optimizer flat
     buffer, the backward finalize kernel += 's into their G slices and no
-    AccumulateGrad kernels run (ops/fused_optim.FLAT_SLICES). Returns the
+    AccumulateGrad kernels run (ops/step_state.py registry). Returns the
     (gw, gb) slices, or (None, None)."""
-    from .fused_optim import flat_grad_slice
-
     gw_sl = flat_grad_slice(weight)
     gb_sl = flat_grad_slice(bias)
     if gw_sl is None or gb_sl is None:
@@ -157,8 +157,6 @@ def _param_grads(weight, bias, gw, gb, direct: bool):
     None after telling the bucketer that the flat G slices were written."""
     if not direct:
         return gw, gb
-    from ..parallel.bucketing import notify_grad_written
-
     notify_grad_written(weight)
     notify_grad_written(bias)
     return None, None
@@ -181,8 +179,6 @@ class _BNAct(torch.autograd.Function):
         defer_gres: bool,
     ):
         C = require_native("batch_norm_act")
-        from .conv import take_conv_stats
-
         conv_part = take_conv_stats(x) if training else None
         x = x.contiguous(memory_format=torch.channels_last)
         out, save_mean, save_invstd = C.bn_act_fwd(
@@ -227,8 +223,6 @@ class _BNAct(torch.autograd.Function):
             # bwd-apply kernel's own mask computation (gres output).
             gres = gres_k if ctx.relu else grad_out
         if ctx.defer_gres:
-            from .conv import stash_junction_gres
-
             stash_junction_gres(ctx.res_key, gres)
             gres = None     # the conv dgrad epilogue folds it into dx
         return gx, gw, gb, None, None, None, None, None, None, gres, None
@@ -244,8 +238,6 @@ class _BNActPool(torch.autograd.Function):
     def forward(ctx, x, weight, bias, running_mean, running_var, training,
                 momentum, eps, kernel, stride, padding):
         C = require_native("batch_norm_act_pool")
-        from .conv import take_conv_stats
-
         conv_part = take_conv_stats(x) if training else None
         x = x.contiguous(memory_format=torch.channels_last)
         out, idx, save_mean, save_invstd = C.bn_act_pool_fwd(

@@ -15,43 +15,12 @@ One kernel launch updates the whole model (~22M elems for ResNet-34): pure
 HBM-bound streaming, vectorized 16B/lane (guide Appendix B elementwise).
 """
 
-
-import weakref
 from typing import List
 
 import torch
 
 from .native import require_native
-
-
-def _bump_wt_marker():
-    # raw-kernel param writes are invisible to autograd version counters;
-    # invalidate the dgrad transposed-weight arena (ops/conv.py)
-    from .conv import bump_conv_wt_marker
-
-    bump_conv_wt_marker()
-
-
-# id(param) -> (flat G tensor, offset, numel, weakref(param)): lets
-# backward ops write gradients straight into the flat buffer (no
-# AccumulateGrad kernel) — see ops/conv.py and ops/functional.py "direct
-# grad" paths. The weakref guards against CPython id reuse: entries are
-# never removed when an optimizer dies, and a NEW parameter allocated at
-# a recycled address must not alias the dead one's slice (silently wrong
-# gradients — caught by the r2 GPU suite).
-FLAT_SLICES = {}
-
-
-def flat_grad_slice(param):
-    """Contiguous flat-G slice backing param.grad, or None."""
-    ent = FLAT_SLICES.get(id(param))
-    if ent is None:
-        return None
-    G, off, n, ref = ent
-    if ref() is not param:          # stale entry from a recycled id
-        del FLAT_SLICES[id(param)]
-        return None
-    return G[off : off + n]
+from .step_state import bump_step_epoch, register_flat_slice
 
 
 class _FlatGroup:
@@ -77,7 +46,7 @@ class _FlatGroup:
             v.copy_(p.data)
             p.data = v
             p.grad = self._view_like(self.G, off, p.data)
-            FLAT_SLICES[id(p)] = (self.G, off, p.numel(), weakref.ref(p))
+            register_flat_slice(p, self.G, off, p.numel())
         self.master = self.P.float() if dt != torch.float32 else None
 
     @staticmethod
@@ -176,7 +145,7 @@ class FusedSGDMomentum(_FlatOptimizer):
                 C = require_native("fused_sgd")
                 C.sgd_step(g.P, g.G, g.master if g.master is not None else g.P,
                            g.V, lr, mom, wd, nesterov)
-                _bump_wt_marker()
+                bump_step_epoch()
             else:
                 master = g.master if g.master is not None else g.P
                 grad = g.G.float()
@@ -215,7 +184,7 @@ class FusedAdam(_FlatOptimizer):
                 C = require_native("fused_adam")
                 C.adam_step(g.P, g.G, g.master if g.master is not None else g.P,
                             g.V, g.S, lr, b1, b2, eps, wd, bc1, bc2)
-                _bump_wt_marker()
+                bump_step_epoch()
             else:
                 master = g.master if g.master is not None else g.P
                 grad = g.G.float()
@@ -383,7 +352,7 @@ class FusedLARS(_FlatOptimizer):
             C.lars_step(g.P, g.G, g.master if g.master is not None else g.P,
                         g.V, t, plan.seg_meta, plan.coef, plan.stats,
                         hp["momentum"], hp["weight_decay"])
-        _bump_wt_marker()
+        bump_step_epoch()
         return None
 
     def _step_reference(self, hp):

@@ -16,33 +16,11 @@ import threading
 import torch
 
 from .native import require_native
+from .step_state import (deferral_ok, has_grad_subscribers,
+                         notify_grad_written)
 
 _TLS = threading.local()
 _META_CACHE = {}
-
-
-def _bucketer_active() -> bool:
-    from ..parallel.bucketing import _NOTIFY
-
-    return bool(_NOTIFY)
-
-
-# Replica threads flag their backwards as non-deferrable (task_ddp sets
-# this around train_step); autograd device workers inherit nothing from
-# the launching thread, so the flag lives in a process-global counter.
-_NO_DEFER = [0]
-
-
-def push_no_defer():
-    _NO_DEFER[0] += 1
-
-
-def pop_no_defer():
-    _NO_DEFER[0] -= 1
-
-
-def _deferral_ok() -> bool:
-    return _NO_DEFER[0] == 0
 
 
 def queue_or_flush(param, g_sl: torch.Tensor, ws_flat: torch.Tensor) -> None:
@@ -57,9 +35,7 @@ def queue_or_flush(param, g_sl: torch.Tensor, ws_flat: torch.Tensor) -> None:
     unverifiable ordering; replicas keep the per-layer immediate flush.
     """
     C = require_native("grad_accum")
-    if _bucketer_active() or not _deferral_ok():
-        from ..parallel.bucketing import notify_grad_written
-
+    if has_grad_subscribers() or not deferral_ok():
         C.grad_accum_bf16(g_sl, ws_flat)
         notify_grad_written(param)
         return

@@ -14,17 +14,20 @@ three GEMMs. conv_igemm requires output channels % 64 == 0 and the FC has
   bias:  db = colsum(dypad)[:N] direct into flat G
 
 The padded weight/bias copies live in a per-device arena refreshed once
-per optimizer step (same freshness marker as the dgrad transpose arena).
+per optimizer step (the step epoch of ops/step_state.py; ops/arenas.py).
 All padding/copy kernels are in-tree (csrc/elementwise.hip) — zero aten
 kernels in the FC path.
 """
 
-import weakref
+import os
 
 import torch
 import torch.nn.functional as F
 
+from .arenas import fc_pad, wgrad_arena, wt_arena
+from .gradflush import queue_or_flush
 from .native import load_native, require_native
+from .step_state import flat_grad_slice, notify_grad_written
 
 
 def _as_nhwc_4d(t2d: torch.Tensor) -> torch.Tensor:
@@ -33,61 +36,13 @@ def _as_nhwc_4d(t2d: torch.Tensor) -> torch.Tensor:
     return t2d.view(M, 1, 1, C).permute(0, 3, 1, 2)
 
 
-class _FcPadArena:
-    """Per-(device, weight) padded weight/bias: wpad [Kp, Cin] bf16 with
-    zero rows >= N, bpad [Kp]. Refreshed when the optimizer marker moves
-    (raw-kernel param updates are invisible to version counters) or the
-    parameter storage is rebound."""
-
-    def __init__(self):
-        self.entries = {}   # id(weight) -> dict
-
-    def get(self, weight, bias):
-        from .conv import _WT_MARKER, _arena_for
-
-        ent = self.entries.get(id(weight))
-        if ent is not None and ent["wref"]() is not weight:
-            ent = None              # CPython recycled a dead weight's id
-        N, Cin = weight.shape
-        Kp = (N + 63) // 64 * 64
-        if ent is None:
-            wpad = torch.zeros(Kp, Cin, dtype=weight.dtype,
-                               device=weight.device)
-            bpad = torch.zeros(Kp, dtype=weight.dtype, device=weight.device)
-            # ONE canonical 4D channels_last view: the transpose arena keys
-            # by id(), so the same view object must be reused everywhere
-            wpad4 = wpad.view(Kp, 1, 1, Cin).permute(0, 3, 1, 2)
-            ent = dict(wpad=wpad, bpad=bpad, wpad4=wpad4, key=None, Kp=Kp,
-                       wref=weakref.ref(weight))
-            self.entries[id(weight)] = ent
-            # register for the batched dgrad transpose: wt[c][k] k-contig
-            _arena_for(wpad4).register(wpad4)
-        key = (_WT_MARKER[0], weight._version,
-               bias._version if bias is not None else 0,
-               weight.data_ptr())
-        if ent["key"] != key:
-            C = require_native("fc_pad")
-            # weight pads along ROWS: rows are contiguous, so the [N,Cin]
-            # -> [Kp,Cin] row pad is a flat [1, N*Cin] -> [1, Kp*Cin] pad
-            C.pad_rows_bf16_into(ent["wpad"].view(1, -1),
-                                 weight.detach().contiguous().view(1, -1))
-            if bias is not None:
-                C.pad_rows_bf16_into(ent["bpad"].view(1, -1),
-                                     bias.detach().reshape(1, -1).contiguous())
-            ent["key"] = key
-        return ent
-
-
-_FC_PAD = _FcPadArena()
-
-
 class _FdaLinear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
         C = require_native("fc_fwd")
 
         N, Cin = weight.shape
-        ent = _FC_PAD.get(weight, bias)
+        ent = ctx.pad = fc_pad(weight, bias)
         Kp = ent["Kp"]
         xc = x.contiguous()
         y = C.conv_igemm_fwd(_as_nhwc_4d(xc), ent["wpad4"],
@@ -103,9 +58,6 @@ class _FdaLinear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         C = require_native("fc_bwd")
-        from .conv import _arena_for
-        from .fused_optim import flat_grad_slice
-        from ..parallel.bucketing import notify_grad_written
 
         x, weight = ctx.saved_tensors
         bias = ctx.bias
@@ -115,25 +67,18 @@ class _FdaLinear(torch.autograd.Function):
         dyp = C.pad_rows_bf16(gy.contiguous(), Kp)     # [M, Kp], pad zero
         dyp4 = _as_nhwc_4d(dyp)
         dx = dw = db = None
-        ent = _FC_PAD.entries[id(weight)]
+        ent = ctx.pad
         if ctx.needs_input_grad[0]:
-            wt = _arena_for(ent["wpad4"]).get(ent["wpad4"])  # [Cin, Kp]
+            wt = wt_arena(x.device).get(ent["wpad4"])  # [Cin, Kp]
             dx4 = C.conv_igemm_dgrad(dyp4, wt, Cin, 1, 1, 1, 1, 1, 1, 0, 0)
             dx = dx4.permute(0, 2, 3, 1).reshape(M, Cin)
         if ctx.needs_input_grad[1]:
             # step-scoped arena slice (pre-zeroed once per backward epoch)
             # instead of a fresh at::zeros per step
-            from .conv import _WS_ARENAS, _WgradArena
-
-            dev = x.device
-            if dev not in _WS_ARENAS:
-                _WS_ARENAS[dev] = _WgradArena(dev)
-            ws = _WS_ARENAS[dev].get(ent["wpad4"])
+            ws = wgrad_arena(x.device).get(ent["wpad4"])
             C.conv_igemm_wgrad_into(dyp4, _as_nhwc_4d(x), ws, 1, 1, 1, 1, 0, 0)
             g_sl = flat_grad_slice(weight)
             if g_sl is not None:
-                from .gradflush import queue_or_flush
-
                 queue_or_flush(weight, g_sl, ws.reshape(-1)[: N * Cin])
             else:
                 dw = ws.view(Kp, Cin)[:N].to(torch.bfloat16)
@@ -148,8 +93,6 @@ class _FdaLinear(torch.autograd.Function):
 
 
 def _fda_linear_supported(x, weight) -> bool:
-    import os
-
     if os.environ.get("FLUXDIST_FC", "") == "lib":
         return False
     if not (x.is_cuda and x.dtype == torch.bfloat16

@@ -22,17 +22,7 @@ import torch
 import torch.distributed as dist
 
 from ..ops.fused_optim import _FlatOptimizer
-
-# Direct-grad notification: backward ops that write gradients straight into
-# the flat G buffer (bypassing AccumulateGrad, so post-accumulate hooks
-# never fire) call notify_grad_written(param) instead. An attached
-# GradBucketer registers itself here.
-_NOTIFY = []
-
-
-def notify_grad_written(param) -> None:
-    for cb in _NOTIFY:
-        cb(param)
+from ..ops.step_state import subscribe_grad_written, unsubscribe_grad_written
 
 
 class GradBucketer:
@@ -110,14 +100,13 @@ class GradBucketer:
             for p in b["params"]:
                 h = p.register_post_accumulate_grad_hook(self._on_grad)
                 self._handles.append(h)
-        _NOTIFY.append(self._on_direct)
+        subscribe_grad_written(self._on_direct)
 
     def detach(self):
         for h in getattr(self, "_handles", []):
             h.remove()
         self._handles = []
-        if self._on_direct in _NOTIFY:
-            _NOTIFY.remove(self._on_direct)
+        unsubscribe_grad_written(self._on_direct)
 
     def _on_direct(self, p):
         if id(p) in self._param2bucket:

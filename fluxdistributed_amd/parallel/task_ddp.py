@@ -44,6 +44,7 @@ from .gradtree import (
     destruct, grads_of, markbuffer_, getbuffer_, sync_buffer,
 )
 from .flatsync import FlatGradReducer
+from ..ops.step_state import no_defer
 from ..utils.device import device_ctx, synchronize, to_device, is_real_gpu
 from ..utils.timers import StageTimers, Throughput
 from ..utils.metrics import topkaccuracy
@@ -144,19 +145,14 @@ def train_step(loss_fn, buffer, replica: Replica, x, y):
     """Forward+backward on one replica, then publish grads to its buffer slot
     (/root/reference/src/ddp_tasks.jl:80-84). In flat mode there are no
     slots (`buffer == {}`): the gradients stay in the replica's flat G."""
-    from ..ops.gradflush import pop_no_defer, push_no_defer
-
     with device_ctx(replica.device):
         replica.optimizer.zero_grad()
         out = replica.model(x)
         loss = loss_fn(out, y)
         # concurrent replica backwards share the autograd device worker:
         # direct-grad flushes must stay per-layer immediate (gradflush.py)
-        push_no_defer()
-        try:
+        with no_defer():
             loss.backward()
-        finally:
-            pop_no_defer()
         if buffer:
             markbuffer_(buffer[replica.index], grads_of(replica.model))
         synchronize(replica.device)
