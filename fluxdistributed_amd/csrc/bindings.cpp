@@ -890,15 +890,119 @@ void conv_igemm_wgrad_into(at::Tensor dy, at::Tensor x, at::Tensor ws,
                            g, cur_stream());
 }
 
+// The chunk plan of a checked wgrad geometry, and its output size K*R*S*C.
+fda::WgradPlan wgrad_plan_of(const fda::ConvGeom& g) {
+    return fda::conv_wgrad_plan(g.rows(fda::CONV_FWD), g.C, g.K, g.R, g.S);
+}
+int64_t wgrad_numel(const fda::ConvGeom& g) {
+    return (int64_t)g.K * g.R * g.S * g.C;
+}
+
+// The slab kernel alone: chunk c of the plan stores its partial gradient
+// into slab[c][K][R*S*C] (fp32, flat, not pre-zeroed; every element is
+// written). For tests and tools/bench_conv.py; wgrad_slab_fold sums it.
+void conv_igemm_wgrad_slabs_into(at::Tensor dy, at::Tensor x, at::Tensor slab,
+                                 int64_t R, int64_t S, int64_t sy, int64_t sx,
+                                 int64_t py, int64_t px) {
+    const char* op = "conv_igemm_wgrad_slabs_into";
+    const auto g = check_wgrad(op, dy, x, R, S, sy, sx, py, px);
+    const auto p = wgrad_plan_of(g);
+    TORCH_CHECK(slab.dim() == 1, op, ": slab must be 1-D");
+    check_flat(op, "slab (one [K][R*S*C] slab per chunk of the plan)", slab,
+               at::kFloat, p.nch * wgrad_numel(g));
+    check_aligned16(op, "slab", slab);
+    check_device(op, {dy, x, slab});
+    fda::conv_wgrad_launch(dy.data_ptr(), x.data_ptr(),
+                           slab.data_ptr<float>(), g, cur_stream(),
+                           fda::WG_SLAB);
+}
+
+// out = slab[0] + slab[1] + ... + slab[nch-1] in that order (out fp32), or
+// out = bf16(f32(out) + that sum) (out bf16: the flat-G accumulate).
+void wgrad_slab_fold(at::Tensor slab, int64_t nch, at::Tensor out) {
+    const char* op = "wgrad_slab_fold";
+    TORCH_CHECK(out.scalar_type() == at::kFloat ||
+                    out.scalar_type() == at::kBFloat16,
+                op, ": out must be fp32 (assign) or bf16 (accumulate)");
+    TORCH_CHECK(out.is_contiguous(), op, ": out must be contiguous");
+    const int64_t n = out.numel();
+    TORCH_CHECK(n >= 4 && n % 4 == 0, op,
+                ": out must hold a positive multiple of 4 elements, got ", n);
+    TORCH_CHECK(nch >= 1 && nch <= INT32_MAX / 2, op, ": bad chunk count ",
+                nch);
+    check_flat(op, "slab (nch slabs of out's size)", slab, at::kFloat,
+               nch * n);
+    check_aligned16(op, "slab", slab);
+    TORCH_CHECK((reinterpret_cast<uintptr_t>(out.data_ptr()) &
+                 (out.scalar_type() == at::kFloat ? 15 : 7)) == 0,
+                op, ": out must be aligned to 4 of its elements");
+    check_device(op, {slab, out});
+    fda::wgrad_slab_fold_launch(slab.data_ptr<float>(), (int)nch, n,
+                                out.data_ptr(),
+                                out.scalar_type() == at::kBFloat16,
+                                cur_stream());
+}
+
+// Slab wgrad plus the bf16 fold into the flat-G slice g ([K][R][S][C] order):
+// g = bf16(f32(g) + dw). The slabs are scratch from the caching allocator,
+// which keeps their reuse stream-ordered and the call capturable.
+void conv_igemm_wgrad_flush(at::Tensor dy, at::Tensor x, at::Tensor g_sl,
+                            int64_t R, int64_t S, int64_t sy, int64_t sx,
+                            int64_t py, int64_t px) {
+    const char* op = "conv_igemm_wgrad_flush";
+    const auto g = check_wgrad(op, dy, x, R, S, sy, sx, py, px);
+    const auto p = wgrad_plan_of(g);
+    const int64_t n = wgrad_numel(g);
+    check_flat(op, "g", g_sl, at::kBFloat16, n);
+    TORCH_CHECK((reinterpret_cast<uintptr_t>(g_sl.data_ptr()) & 7) == 0, op,
+                ": g must be 8-byte aligned");
+    check_device(op, {dy, x, g_sl});
+    auto slab = at::empty({p.nch * n}, x.options().dtype(at::kFloat));
+    fda::conv_wgrad_launch(dy.data_ptr(), x.data_ptr(),
+                           slab.data_ptr<float>(), g, cur_stream(),
+                           fda::WG_SLAB);
+    fda::wgrad_slab_fold_launch(slab.data_ptr<float>(), p.nch, n,
+                                g_sl.data_ptr(), true, cur_stream());
+}
+
+// The allocating fp32 form: slabs plus the fp32 fold where the rule says so
+// (conv_igemm_wgrad_mode), else a zeroed workspace and the atomic kernel.
 at::Tensor conv_igemm_wgrad(at::Tensor dy, at::Tensor x,
                             int64_t R, int64_t S,
                             int64_t sy, int64_t sx, int64_t py, int64_t px) {
-    TORCH_CHECK(dy.dim() == 4 && x.dim() == 4,
-                "conv_igemm_wgrad: dy and x must be 4-D");
-    auto ws = at::zeros({dy.size(1), R * S * x.size(1)},
-                        x.options().dtype(at::kFloat));
-    conv_igemm_wgrad_into(dy, x, ws, R, S, sy, sx, py, px);
+    const char* op = "conv_igemm_wgrad";
+    TORCH_CHECK(dy.dim() == 4 && x.dim() == 4, op,
+                ": dy and x must be 4-D");
+    const auto g = check_wgrad(op, dy, x, R, S, sy, sx, py, px);
+    const auto p = wgrad_plan_of(g);
+    const int64_t n = wgrad_numel(g);
+    check_device(op, {dy, x});
+    const auto f32 = x.options().dtype(at::kFloat);
+    if (!fda::conv_wgrad_use_slabs(p, n)) {
+        auto ws = at::zeros({g.K, n / g.K}, f32);
+        fda::conv_wgrad_launch(dy.data_ptr(), x.data_ptr(),
+                               ws.data_ptr<float>(), g, cur_stream());
+        return ws;
+    }
+    auto slab = at::empty({p.nch * n}, f32);
+    auto ws = at::empty({g.K, n / g.K}, f32);
+    fda::conv_wgrad_launch(dy.data_ptr(), x.data_ptr(), slab.data_ptr<float>(),
+                           g, cur_stream(), fda::WG_SLAB);
+    fda::wgrad_slab_fold_launch(slab.data_ptr<float>(), p.nch, n,
+                                ws.data_ptr(), false, cur_stream());
     return ws;
+}
+
+// "slab" or "atomic": what conv_igemm_wgrad runs for a body wgrad with
+// M = N*P*Q pixels, and what the train step asks before it chooses between
+// conv_igemm_wgrad_flush and the arena path.
+std::string conv_igemm_wgrad_mode(int64_t M, int64_t C, int64_t K, int64_t R,
+                                  int64_t S) {
+    TORCH_CHECK(M >= 1 && M <= INT32_MAX && C >= 64 && C % 64 == 0 &&
+                    K >= 64 && K % 64 == 0 && R >= 1 && S >= 1,
+                "conv_igemm_wgrad_mode: bad geometry");
+    const auto p = fda::conv_wgrad_plan(M, (int)C, (int)K, (int)R, (int)S);
+    return fda::conv_wgrad_use_slabs(p, K * R * S * C) ? "slab" : "atomic";
 }
 
 // Operand checks shared by the stem entry points, and their geometry. x8:
@@ -1390,6 +1494,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "Block id -> (ktile, ctile, rs, chunk) of a wgrad grid");
     m.def("conv_igemm_wgrad", &conv_igemm_wgrad,
           "implicit-GEMM conv weight-grad (NHWC bf16, MFMA + tr16 reads)");
+    m.def("conv_igemm_wgrad_slabs_into", &conv_igemm_wgrad_slabs_into,
+          "wgrad with one fp32 slab per chunk, plain stores, no atomics");
+    m.def("wgrad_slab_fold", &wgrad_slab_fold,
+          "ordered sum of wgrad slabs into fp32 (assign) or bf16 (+=)");
+    m.def("conv_igemm_wgrad_flush", &conv_igemm_wgrad_flush,
+          "slab wgrad + ordered fold accumulated into a bf16 flat-G slice");
+    m.def("conv_igemm_wgrad_mode", &conv_igemm_wgrad_mode,
+          "'slab' or 'atomic': the path a body wgrad with M pixels takes");
     m.def("conv_igemm_dgrad", &conv_igemm_dgrad,
           "implicit-GEMM conv input-grad (NHWC bf16, MFMA; optional fused "
           "+= accum epilogue)",

@@ -35,7 +35,8 @@
 // fwd+dgrad x 2 tiles x {BK64 2-buf, BK32 3-ring} (8) + the stem (1), the
 // four fwd configs and the stem once more with the inference epilogue
 // (EpiInfer: eval BN + residual + ReLU before the single bf16 round),
-// conv_wgrad_kernel FT2 / FT2-stem / FT4 (3), conv_skcombine_kernel (plain
+// conv_wgrad_kernel FT2 / FT2-stem / FT4 (3) and FT2 / FT4 once more with
+// the slab epilogue (2), conv_skcombine_kernel (plain
 // and EpiInfer), wt_transpose_kernel. Variants that were measured and rejected are
 // recorded in profiles/ab_conv8.md, profiles/ab_bigtile.md and
 // docs/wgrad_study.md, not kept here.
@@ -56,8 +57,9 @@
 // channel-padded C=8 image, r-only tap loop), the wgrad kernel
 // (reduction along the pixel axis via ds_read_tr16_b64 hardware
 // transpose reads from an m4-grouped LDS image, window positions
-// permuted for bank-conflict-free half-wave reads, fp32 atomic chunk
-// accumulation), and the batched weight transposer for the dgrad B
+// permuted for bank-conflict-free half-wave reads, chunks accumulated with
+// fp32 atomics or stored as per-chunk fp32 slabs for an ordered fold,
+// profiles/wgrad_slab.md), and the batched weight transposer for the dgrad B
 // layout. The wgrad grid is 1-D: a block id maps through an XCD-contiguous
 // logical id, pixel chunk slowest, to (k-tile, c-tile, tap, chunk)
 // (wgrad_block_coords, fda_kernels.h), so the blocks that stage one
@@ -911,16 +913,20 @@ typedef __attribute__((ext_vector_type(4))) short short4_;
 // 32 MFMAs — chosen by channel divisibility; the bigger tile quadruples
 // the MFMA-per-glds ratio) for one (r,s) tap and one M-chunk of pixels
 // (conv_wgrad_plan sizes it; the stem uses 8 * WG_MCH); chunks accumulate
-// into an fp32 workspace with atomicAdd.
+// into an fp32 workspace with atomicAdd (WG_ATOMIC), or each chunk stores
+// its tile into its own fp32 slab (WG_SLAB) and wgrad_slab_fold_kernel sums
+// the slabs in chunk order.
 constexpr int WG_BM = 64;      // m per K-step
 constexpr int WG_MCH = 2048;   // chunk of small problems, the stem's unit
 
-template <int FT, bool STEM = false>
+template <int FT, bool STEM = false, int EPI = WG_ATOMIC>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(
     const unsigned short* __restrict__ dy,   // [M][K] (NHWC out grad)
     const unsigned short* __restrict__ x,    // [N,H,W,C]
-    float* __restrict__ ws,  /* [K][RS*C] fp32, pre-zeroed, accumulated
-                                with atomicAdd across chunks */
+    float* __restrict__ ws,  /* WG_ATOMIC: [K][RS*C] fp32, pre-zeroed,
+                                accumulated with atomicAdd across chunks;
+                                WG_SLAB: [nch][K][RS*C] fp32, every element
+                                stored once */
     int N, int H, int W, int C, int K, int P, int Q,
     int R, int S, int sy, int sx, int py, int px, int nch, int mch) {
     constexpr int MB = WG_BM;                // m per K-step
@@ -1119,6 +1125,13 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(
     // epilogue: out[i=k][j=c]; C/D map col=lane&15, row=(lane>>4)*4+jj
     const int fcol = lane & 15, frow0 = (lane >> 4) * 4;
     const long RSC = (long)R * S * C;
+    // WG_SLAB: the whole tile goes to the chunk's own slab, once, with plain
+    // stores (rows past mend were staged as zeros, so a ragged last chunk
+    // still writes every element). Stored from the fragment layout, four
+    // 64-B row pieces per wave-instruction: the LDS-staged 16-B form of the
+    // dgrad epilogue measured the same here (profiles/wgrad_slab.md).
+    float* o = ws;
+    if constexpr (EPI == WG_SLAB) o += (long)chunk * K * RSC;
     #pragma unroll
     for (int ki = 0; ki < FT; ++ki)
         #pragma unroll
@@ -1127,8 +1140,9 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(
             for (int jj = 0; jj < 4; ++jj) {
                 const int kk = k0 + wk * 16 * FT + ki * 16 + frow0 + jj;
                 const int cc = c0 + wc * 16 * FT + ci * 16 + fcol;
-                atomicAdd(&ws[kk * RSC + (long)rs * C + cc],
-                          acc[ki][ci][jj]);
+                float* p = &o[kk * RSC + (long)rs * C + cc];
+                if constexpr (EPI == WG_SLAB) *p = acc[ki][ci][jj];
+                else atomicAdd(p, acc[ki][ci][jj]);
             }
 }
 
@@ -1193,10 +1207,25 @@ WgradPlan conv_wgrad_plan(long M, int C, int K, int R, int S) {
     return p;
 }
 
+// Slabs or atomics. One or two chunks stay on atomics: at most two addends
+// per address are order-independent already, and a fold would only add a
+// pass. Beyond that the slab path trades nch*n*4 bytes of atomics (about
+// 1.3 TB/s) for as many bytes of plain stores, the fold's read of them and
+// one more dependent launch, about 5 us: measured per call, it saves 5 to
+// 10 us at 28 to 33 MB (the four FT4 flagship shapes) and loses 1 to 13 us
+// at 5.5 to 12.4 MB (the six FT2 ones), with break-even near 13 MB by that
+// model. The threshold sits between the two measured groups
+// (profiles/wgrad_slab.md).
+constexpr long WG_SLAB_MIN_BYTES = 24L << 20;
+
+bool conv_wgrad_use_slabs(const WgradPlan& p, long n) {
+    return p.nch >= 3 && (long)p.nch * n * 4 >= WG_SLAB_MIN_BYTES;
+}
+
 void conv_wgrad_launch(const void* dy, const void* x, float* ws,
-                       const ConvGeom& g, hipStream_t stream) {
+                       const ConvGeom& g, hipStream_t stream, int epi) {
     const WgradPlan p = conv_wgrad_plan(g.rows(CONV_FWD), g.C, g.K, g.R, g.S);
-    // one argument list for both tile sizes
+    // one argument list for both tile sizes and every epilogue
     auto launch = [&](auto kern, size_t shmem) {
         hipLaunchKernelGGL(kern, dim3((unsigned)p.nwg), dim3(256), shmem,
                            stream, (const unsigned short*)dy,
@@ -1204,12 +1233,15 @@ void conv_wgrad_launch(const void* dy, const void* x, float* ws,
                            g.K, g.P, g.Q, g.R, g.S, g.sy, g.sx, g.py, g.px,
                            p.nch, p.mch);
     };
-    if (p.ft == 4)
-        launch(conv_wgrad_kernel<4>,
-               2 * 2 * (WG_BM * 128) * sizeof(unsigned short));
-    else
-        launch(conv_wgrad_kernel<2>,
-               3 * 2 * (WG_BM * 64) * sizeof(unsigned short));
+    dispatch_flag(epi == WG_SLAB, [&](auto slab) {
+        constexpr int EPI = decltype(slab)::value ? WG_SLAB : WG_ATOMIC;
+        if (p.ft == 4)
+            launch(conv_wgrad_kernel<4, false, EPI>,
+                   2 * 2 * (WG_BM * 128) * sizeof(unsigned short));
+        else
+            launch(conv_wgrad_kernel<2, false, EPI>,
+                   3 * 2 * (WG_BM * 64) * sizeof(unsigned short));
+    });
 }
 
 }  // namespace fda

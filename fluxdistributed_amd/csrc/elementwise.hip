@@ -414,6 +414,60 @@ void grad_accum_batch_launch(const long* g_ptrs, const long* ws_ptrs,
                        g_ptrs, ws_ptrs, ns);
 }
 
+// Ordered fold of the wgrad slabs (conv_wgrad_kernel, WG_SLAB): element i of
+// the result is ((slab[0][i] + slab[1][i]) + slab[2][i]) + ..., fp32 adds
+// strictly in chunk order, no atomics and no split of the chunk range, so
+// the bits do not depend on the run. A lane owns 4 consecutive elements (8
+// measured slower alone and the same inside the flush,
+// profiles/wgrad_slab.md) and reads 16 B per slab, four chunks' loads in
+// flight before their adds. BF16: g = bf16(f32(g) + s), the expression of
+// grad_accum_bf16_kernel; else out = s in fp32. n % 4 == 0.
+template <bool BF16>
+__global__ __launch_bounds__(256) void wgrad_slab_fold_kernel(
+    const float* __restrict__ slab, int nch, long n, void* __restrict__ out) {
+    constexpr int U = 4;
+    const long i0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i0 >= n) return;
+    const float* p = slab + i0;
+    float4 s = *(const float4*)p;
+    int c = 1;
+    for (; c + U <= nch; c += U) {
+        float4 t[U];
+        #pragma unroll
+        for (int u = 0; u < U; ++u)
+            t[u] = *(const float4*)(p + (long)(c + u) * n);
+        #pragma unroll
+        for (int u = 0; u < U; ++u) {
+            s.x += t[u].x; s.y += t[u].y; s.z += t[u].z; s.w += t[u].w;
+        }
+    }
+    for (; c < nch; ++c) {
+        const float4 t = *(const float4*)(p + (long)c * n);
+        s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
+    }
+    if constexpr (BF16) {
+        unsigned short* g = (unsigned short*)out + i0;
+        unsigned short gv[4];
+        *(uint2*)gv = *(const uint2*)g;
+        const float sv[4] = {s.x, s.y, s.z, s.w};
+        #pragma unroll
+        for (int e = 0; e < 4; ++e)
+            gv[e] = f32_to_bf16bits(bf16bits_to_f32(gv[e]) + sv[e]);
+        *(uint2*)g = *(const uint2*)gv;
+    } else {
+        *(float4*)((float*)out + i0) = s;
+    }
+}
+
+void wgrad_slab_fold_launch(const float* slab, int nch, long n, void* out,
+                            bool out_bf16, hipStream_t s) {
+    const dim3 grid((unsigned)((n / 4 + 255) / 256));
+    dispatch_flag(out_bf16, [&](auto b) {
+        hipLaunchKernelGGL((wgrad_slab_fold_kernel<decltype(b)::value>), grid,
+                           dim3(256), 0, s, slab, nch, n, out);
+    });
+}
+
 // --------------------------------------------------------------------------
 // FC head support (ops/linear.py): the Dense layer runs on the conv
 // implicit-GEMM kernels with out_features padded to a multiple of 64

@@ -267,9 +267,28 @@ __host__ __device__ __forceinline__ WgradCoords wgrad_block_coords(
     return c;
 }
 
-// wgrad: ws[K][RS*C] fp32 (pre-zeroed) += dy^T @ im2col(x), atomic chunks.
+// How the chunks of a wgrad meet. WG_ATOMIC: ws[K][RS*C] fp32 (pre-zeroed)
+// += every chunk's tile, with atomicAdd. WG_SLAB: ws is [nch][K][RS*C] fp32
+// and chunk c stores its tiles into slab c with plain stores, every element
+// exactly once (no pre-zeroing); wgrad_slab_fold_launch sums the slabs.
+constexpr int WG_ATOMIC = 0;
+constexpr int WG_SLAB = 1;
+
+// wgrad: dy^T @ im2col(x) into ws, by the plan of conv_wgrad_plan.
 void conv_wgrad_launch(const void* dy, const void* x, float* ws,
-                       const ConvGeom& g, hipStream_t stream);
+                       const ConvGeom& g, hipStream_t stream,
+                       int epi = WG_ATOMIC);
+
+// Whether a body wgrad of that plan with n = K*R*S*C outputs takes the slab
+// path where the caller has the choice (conv_igemm_wgrad, the train step).
+bool conv_wgrad_use_slabs(const WgradPlan& p, long n);
+
+// Ordered fold of wgrad slabs: s = slab[0] + slab[1] + ... + slab[nch-1],
+// fp32 adds strictly in that order, so the sum is the same bits on every
+// run. out_bf16: g = bf16(f32(g) + s), the direct-grad flush of
+// grad_accum_bf16_launch; else out (fp32) = s. n % 4 == 0, 16-B aligned.
+void wgrad_slab_fold_launch(const float* slab, int nch, long n, void* out,
+                            bool out_bf16, hipStream_t s);
 
 // batched conv-weight transpose: w[k][rc] -> wt[rc][k] for all tensors in
 // one launch (device pointer arrays)

@@ -95,7 +95,9 @@ class _WtArena:
 class _WgradArena:
     """Step-scoped fp32 wgrad workspace: zeroed in ONE launch per backward
     epoch instead of a per-layer `zeros` each (the wgrad kernel accumulates
-    into its slice with atomicAdd). A second wgrad call for the same weight
+    into its slice with atomicAdd). Only weights whose wgrad runs the atomic
+    kernel ever ask for a slot: the slab path (conv_igemm_wgrad_flush) writes
+    flat G itself. A second wgrad call for the same weight
     inside one epoch (gradient micro-accumulation) re-zeros just its slice
     so the returned dw stays the per-backward gradient. Slot offsets are
     append-only: a dead weight's slot is not reused."""

@@ -13,6 +13,9 @@ fall back to the library path.
 Env:
   FLUXDIST_CONV=miopen   force the library path everywhere (A/B testing)
   FLUXDIST_CONV=fda      force the native path (errors on unsupported)
+  FLUXDIST_WGRAD_SLAB=0  weight-grads into flat G: atomic workspace + queued
+                         flush for every shape (default 1: slabs + ordered
+                         fold where conv_igemm_wgrad_mode says "slab")
 """
 
 import os
@@ -24,7 +27,8 @@ import torch.nn.functional as F
 from .arenas import stem_pool_get, stem_pool_put, wgrad_arena, wt_arena
 from .gradflush import queue_or_flush
 from .native import load_native, require_native
-from .step_state import (clear_conv_stats, flat_grad_slice, stash_conv_stats,
+from .step_state import (clear_conv_stats, flat_grad_slice,
+                         notify_grad_written, stash_conv_stats,
                          take_junction_gres)
 # names that callers outside ops/ import from here
 from .step_state import bump_step_epoch as bump_conv_wt_marker  # noqa: F401
@@ -62,7 +66,10 @@ class _FdaConv2d(torch.autograd.Function):
     """Forward, input-grad and weight-grad on the native implicit-GEMM
     kernels. The weight-grad lands in an fp32 workspace and, when the
     weight lives in a fused optimizer's flat buffer, is flushed straight
-    into its G slice. FLUXDIST_WGRAD=miopen routes the weight-grad alone to
+    into its G slice; shapes for which conv_igemm_wgrad_mode says "slab"
+    skip the workspace and go through per-chunk slabs and an ordered fold
+    (conv_igemm_wgrad_flush; FLUXDIST_WGRAD_SLAB=0 keeps them on the atomic
+    workspace path). FLUXDIST_WGRAD=miopen routes the weight-grad alone to
     the library (aten convolution_backward with a weight-only mask)."""
 
     @staticmethod
@@ -110,6 +117,17 @@ class _FdaConv2d(torch.autograd.Function):
             if os.environ.get("FLUXDIST_WGRAD", "") != "miopen":
                 C = require_native("conv_igemm_wgrad")
                 g_sl = flat_grad_slice(w) if cacheable else None
+                if (g_sl is not None
+                        and os.environ.get("FLUXDIST_WGRAD_SLAB", "1") != "0"
+                        and C.conv_igemm_wgrad_mode(
+                            gy.shape[0] * gy.shape[2] * gy.shape[3],
+                            Cin, K, R, S) == "slab"):
+                    # per-chunk fp32 slabs + ordered fold straight into the
+                    # G slice: no arena slot, no zero fill, no queued flush
+                    C.conv_igemm_wgrad_flush(gy, x, g_sl, R, S, sy, sx,
+                                             py, px)
+                    notify_grad_written(w)
+                    return dx, None, None, None, None
                 if cacheable:
                     ws = wgrad_arena(w.device).get(w)
                     C.conv_igemm_wgrad_into(gy, x, ws, R, S, sy, sx, py, px)

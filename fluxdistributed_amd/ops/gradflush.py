@@ -7,6 +7,9 @@ per-layer flush launches of a ResNet-34 backward are queued and executed
 as ONE batched kernel at backward end via autograd's engine callback —
 per-layer launches measured ~180 us/step of mostly launch+tail overhead.
 
+Only the atomic wgrad path comes through here: a wgrad that takes the slab
+path folds its slabs into the G slice in its own launch (ops/conv.py).
+
 The queue holds references to the workspace tensors so the caching
 allocator cannot recycle them before the batched kernel reads them.
 """

@@ -104,15 +104,20 @@ def dgrad_arms(args):
 def wgrad_arms(args):
     """Weight-grad arms: the kernel alone, accumulating into one workspace
     (conv_igemm_wgrad_into, as the train step calls it), and with the
-    workspace allocation and zero fill (conv_igemm_wgrad). Figures as for
+    workspace allocation and zero fill on a shape the rule keeps on atomics
+    or the slabs and the fp32 fold on one it does not (conv_igemm_wgrad), and
+    the slab kernel plus the ordered bf16 fold into a flat-G slice
+    (conv_igemm_wgrad_flush, the train step's call where
+    conv_igemm_wgrad_mode says "slab"; timed on every shape). Figures as for
     --mode dgrad: the median of --repeats timed blocks and their min..max."""
     C_ = require_native("conv_igemm_wgrad_into")
     n = args.batch
     print(f"# batch={n} wgrad, us per call: median (min..max) of "
           f"{args.repeats} blocks of {args.iters} calls")
-    print(f"{'shape':34s} {'kernel (into)':>22s} {'with zero fill':>22s}")
+    print(f"{'shape':34s} {'kernel (into)':>22s} {'allocating form':>22s} "
+          f"{'slabs + fold':>22s}  mode")
     shapes = SHAPES if args.only < 0 else [SHAPES[args.only]]
-    tot = [0.0, 0.0]
+    tot = [0.0, 0.0, 0.0]
     for (c, h, w, k, r, s, cnt) in shapes:
         pad = r // 2
         P, Q = (h + 2 * pad - r) // s + 1, (w + 2 * pad - r) // s + 1
@@ -121,9 +126,11 @@ def wgrad_arms(args):
         x = torch.randn(n, c, h, w, device="cuda").bfloat16() \
             .contiguous(memory_format=torch.channels_last)
         ws = torch.zeros(k * r * r * c, device="cuda")
+        g = torch.zeros(k * r * r * c, device="cuda", dtype=torch.bfloat16)
         arms = [
             lambda: C_.conv_igemm_wgrad_into(gy, x, ws, r, r, s, s, pad, pad),
             lambda: C_.conv_igemm_wgrad(gy, x, r, r, s, s, pad, pad),
+            lambda: C_.conv_igemm_wgrad_flush(gy, x, g, r, r, s, s, pad, pad),
         ]
         cells = []
         # blocks of the arms in turn, so drift hits every arm alike
@@ -137,8 +144,11 @@ def wgrad_arms(args):
             tot[i] += med * cnt
             cells.append(f"{med:7.1f} ({t[0]:.1f}..{t[-1]:.1f})")
         name = f"{c}x{h}x{w} k{k} {r}x{r} s{s} x{cnt}"
-        print(f"{name:34s} {cells[0]:>22s} {cells[1]:>22s}")
-    print(f"{'TOTAL (weighted by layer count)':34s} {tot[0]:22.1f} {tot[1]:22.1f}")
+        mode = C_.conv_igemm_wgrad_mode(n * P * Q, c, k, r, r)
+        print(f"{name:34s} {cells[0]:>22s} {cells[1]:>22s} {cells[2]:>22s}"
+              f"  {mode}")
+    print(f"{'TOTAL (weighted by layer count)':34s} {tot[0]:22.1f} "
+          f"{tot[1]:22.1f} {tot[2]:22.1f}")
 
 
 def main():
