@@ -1005,6 +1005,108 @@ std::string conv_igemm_wgrad_mode(int64_t M, int64_t C, int64_t K, int64_t R,
     return fda::conv_wgrad_use_slabs(p, K * R * S * C) ? "slab" : "atomic";
 }
 
+// ---- fp32 conv on the fp32 MFMA (conv_f32.hip) ----------------------------
+// Operands: channels_last fp32 activations and the channels_last fp32 weight
+// [K][R][S][C] as stored, for all three kernels. Checks in the order of the
+// bf16 entry points: dtype, layout, geometry, sizes, then the device.
+
+void check_cl_f32(const char* op, const char* name, const at::Tensor& t) {
+    TORCH_CHECK(t.dim() == 4 && t.scalar_type() == at::kFloat &&
+                    t.is_contiguous(at::MemoryFormat::ChannelsLast),
+                op, ": ", name, " must be 4-D channels_last fp32");
+    check_aligned16(op, name, t);
+}
+
+at::Tensor conv_f32_fwd(at::Tensor x, at::Tensor w, int64_t sy, int64_t sx,
+                        int64_t py, int64_t px) {
+    const char* op = "conv_f32_fwd";
+    check_cl_f32(op, "x", x);
+    check_cl_f32(op, "w", w);
+    const auto g = conv_geometry(op, x.size(0), x.size(1), x.size(2),
+                                 x.size(3), w.size(0), w.size(2), w.size(3),
+                                 sy, sx, py, px);
+    TORCH_CHECK(w.size(1) == x.size(1), op, ": channel mismatch: x has ",
+                x.size(1), ", w has ", w.size(1));
+    check_device(op, {x, w});
+    auto y = at::empty({g.N, g.K, g.P, g.Q},
+                       x.options().memory_format(at::MemoryFormat::ChannelsLast));
+    fda::conv_f32_launch(x.data_ptr<float>(), w.data_ptr<float>(),
+                         y.data_ptr<float>(), g, fda::CONV_FWD, cur_stream());
+    return y;
+}
+
+// dy [N,K,P,Q], w [K,C,R,S] -> dx [N,C,H,W]
+at::Tensor conv_f32_dgrad(at::Tensor dy, at::Tensor w, int64_t H, int64_t W,
+                          int64_t sy, int64_t sx, int64_t py, int64_t px) {
+    const char* op = "conv_f32_dgrad";
+    check_cl_f32(op, "dy", dy);
+    check_cl_f32(op, "w", w);
+    const auto g = conv_geometry(op, dy.size(0), w.size(1), H, W, w.size(0),
+                                 w.size(2), w.size(3), sy, sx, py, px);
+    TORCH_CHECK(dy.size(1) == w.size(0), op, ": channel mismatch: dy has ",
+                dy.size(1), ", w has ", w.size(0));
+    check_dy(op, dy, g);
+    check_device(op, {dy, w});
+    auto dx = at::empty({g.N, g.C, g.H, g.W},
+                        dy.options().memory_format(at::MemoryFormat::ChannelsLast));
+    fda::conv_f32_launch(dy.data_ptr<float>(), w.data_ptr<float>(),
+                         dx.data_ptr<float>(), g, fda::CONV_DGRAD,
+                         cur_stream());
+    return dx;
+}
+
+// dy [N,K,P,Q], x [N,C,H,W] -> ws [K][R*S*C] fp32: the channels_last weight
+// memory order, so dw is a view of it. More than one chunk: per-chunk slabs
+// from the caching allocator and the ordered fp32 fold.
+at::Tensor conv_f32_wgrad(at::Tensor dy, at::Tensor x, int64_t R, int64_t S,
+                          int64_t sy, int64_t sx, int64_t py, int64_t px) {
+    const char* op = "conv_f32_wgrad";
+    check_cl_f32(op, "dy", dy);
+    check_cl_f32(op, "x", x);
+    const auto g = conv_geometry(op, x.size(0), x.size(1), x.size(2),
+                                 x.size(3), dy.size(1), R, S, sy, sx, py, px);
+    TORCH_CHECK(dy.size(0) == x.size(0), op, ": batch size mismatch: dy has ",
+                dy.size(0), ", x has ", x.size(0));
+    check_dy(op, dy, g);
+    const auto p = fda::conv_f32_wgrad_plan(g.rows(fda::CONV_FWD), g.C, g.K,
+                                            g.R, g.S);
+    const int64_t n = wgrad_numel(g);
+    check_device(op, {dy, x});
+    const auto f32 = x.options().memory_format(at::MemoryFormat::Contiguous);
+    auto ws = at::empty({g.K, n / g.K}, f32);
+    if (p.nch == 1) {
+        fda::conv_f32_wgrad_launch(dy.data_ptr<float>(), x.data_ptr<float>(),
+                                   ws.data_ptr<float>(), g, cur_stream());
+        return ws;
+    }
+    auto slab = at::empty({p.nch * n}, f32);
+    fda::conv_f32_wgrad_launch(dy.data_ptr<float>(), x.data_ptr<float>(),
+                               slab.data_ptr<float>(), g, cur_stream());
+    fda::wgrad_slab_fold_launch(slab.data_ptr<float>(), p.nch, n,
+                                ws.data_ptr(), false, cur_stream());
+    return ws;
+}
+
+// What the fp32 kernels run for a problem. mode "fwd" / "dgrad": M output
+// rows (dgrad: of the largest parity class) -> (BM, BN, 1, M). mode "wgrad":
+// M = N*P*Q pixels -> (tile, tile, nch, mch).
+std::tuple<int64_t, int64_t, int64_t, int64_t> conv_f32_config(
+    int64_t M, int64_t C, int64_t K, int64_t R, int64_t S,
+    const std::string& mode) {
+    TORCH_CHECK(M >= 1 && M <= INT32_MAX && C >= 64 && C % 64 == 0 &&
+                    K >= 64 && K % 64 == 0 && R >= 1 && S >= 1,
+                "conv_f32_config: bad geometry");
+    if (mode == "wgrad") {
+        const auto p = fda::conv_f32_wgrad_plan(M, (int)C, (int)K, (int)R,
+                                                (int)S);
+        return {p.tile, p.tile, p.nch, p.mch};
+    }
+    TORCH_CHECK(mode == "fwd" || mode == "dgrad",
+                "conv_f32_config: mode must be fwd, dgrad or wgrad");
+    const auto p = fda::conv_f32_plan(M, (int)(mode == "fwd" ? K : C), 1);
+    return {p.bm, p.bn, 1, M};
+}
+
 // Operand checks shared by the stem entry points, and their geometry. x8:
 // [N,8,Hp,Wp] channels_last bf16 (spatially pre-padded, channels 3..7
 // zero). Output pixel (p, q) reads filter row r from input row p*sy + r,
@@ -1502,6 +1604,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "slab wgrad + ordered fold accumulated into a bf16 flat-G slice");
     m.def("conv_igemm_wgrad_mode", &conv_igemm_wgrad_mode,
           "'slab' or 'atomic': the path a body wgrad with M pixels takes");
+    m.def("conv_f32_fwd", &conv_f32_fwd,
+          "fp32 implicit-GEMM conv forward (NHWC fp32, fp32 MFMA)");
+    m.def("conv_f32_dgrad", &conv_f32_dgrad,
+          "fp32 conv input-grad from the untransposed weight");
+    m.def("conv_f32_wgrad", &conv_f32_wgrad,
+          "fp32 conv weight-grad: per-chunk slabs + ordered fold, no atomics");
+    m.def("conv_f32_config", &conv_f32_config,
+          "(BM, BN, nch, mch) the fp32 conv kernels run; mode fwd/dgrad/wgrad");
     m.def("conv_igemm_dgrad", &conv_igemm_dgrad,
           "implicit-GEMM conv input-grad (NHWC bf16, MFMA; optional fused "
           "+= accum epilogue)",

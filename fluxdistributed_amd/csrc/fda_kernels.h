@@ -290,6 +290,35 @@ bool conv_wgrad_use_slabs(const WgradPlan& p, long n);
 void wgrad_slab_fold_launch(const float* slab, int nch, long n, void* out,
                             bool out_bf16, hipStream_t s);
 
+// fp32 conv on the fp32 MFMA (conv_f32.hip). Geometry and modes as above;
+// every operand is fp32, and the weight is always w [K][R*S*C] as stored:
+// the dgrad reads it untransposed.
+// What a fwd / dgrad launch runs: the block tile (128x128 on four waves or
+// 64x64 on one) and the grid size over all parity classes. M = g.rows(mode).
+struct ConvF32Plan {
+    int bm, bn;
+    long blocks;
+};
+ConvF32Plan conv_f32_plan(long M, int OC, int classes);
+// fwd:   src=x [N,H,W,C],  out=y [N*P*Q][K]
+// dgrad: src=dy [N,P,Q,K], out=dx [N,H,W,C]
+void conv_f32_launch(const float* src, const float* wgt, float* out,
+                     const ConvGeom& g, ConvMode mode, hipStream_t stream);
+
+// What a wgrad of M = N*P*Q pixels runs: a tile x tile block of dw[k][c]
+// per filter tap, mch pixels per chunk (whole 32-pixel K-steps), nch chunks,
+// nwg = (K/tile)*(C/tile)*R*S*nch blocks decoded by wgrad_block_coords.
+struct WgradF32Plan {
+    int tile, mch, nch;
+    long nwg;
+};
+WgradF32Plan conv_f32_wgrad_plan(long M, int C, int K, int R, int S);
+// nch == 1: ws is the result [K][R*S*C]. nch > 1: ws is [nch][K][R*S*C] and
+// chunk c stores into slab c; wgrad_slab_fold_launch sums them. Every
+// element is written exactly once either way (nothing is pre-zeroed).
+void conv_f32_wgrad_launch(const float* dy, const float* x, float* ws,
+                           const ConvGeom& g, hipStream_t stream);
+
 // batched conv-weight transpose: w[k][rc] -> wt[rc][k] for all tensors in
 // one launch (device pointer arrays)
 void wt_transpose_launch(const long* src_ptrs, long* dst_ptrs, const int* Ks,

@@ -10,9 +10,23 @@ ImageNet 7x7 and CIFAR 3x3 stems) run on the dedicated CONV_STEM kernels;
 only genuinely unsupported shapes (grouped/dilated, odd channel counts)
 fall back to the library path.
 
+fp32 operands have a native path of their own, csrc/conv_f32.hip on the
+fp32 MFMA (v_mfma_f32_16x16x4_f32): the same constraints (NHWC, dilation 1,
+groups 1, C and K multiples of 64), forward, dgrad from the untransposed
+weight and wgrad through per-chunk slabs and an ordered fold. It is plain
+autograd: no conv->BN stats, no junction fusion, no arenas, no direct write
+into flat G. The fp32 stem (C=3) and the fp32 FC head stay on the library.
+The path is opt-in (FLUXDIST_CONV_F32=1): measured against the library's
+fp32 conv it is slower on every ResNet-34 shape and leg (profiles/conv_f32.md),
+so by the rule that defaults are measured winners the default is 0.
+
 Env:
   FLUXDIST_CONV=miopen   force the library path everywhere (A/B testing)
-  FLUXDIST_CONV=fda      force the native path (errors on unsupported)
+  FLUXDIST_CONV=fda      force the native path (errors on shapes neither
+                         native path supports)
+  FLUXDIST_CONV_F32=1|0  fp32 body convs on conv_f32.hip (1) or the library
+                         (0, the default). Read at call time. FLUXDIST_CONV=fda
+                         implies 1.
   FLUXDIST_WGRAD_SLAB=0  weight-grads into flat G: atomic workspace + queued
                          flush for every shape (default 1: slabs + ordered
                          fold where conv_igemm_wgrad_mode says "slab")
@@ -44,6 +58,24 @@ def _native_supported(x: torch.Tensor, w: torch.Tensor, stride, padding,
     if os.environ.get("FLUXDIST_CONV", "") == "miopen":
         return False
     if not (x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16):
+        return False
+    if groups != 1 or _pair(dilation) != (1, 1):
+        return False
+    C, K = x.shape[1], w.shape[0]
+    if C % 64 != 0 or K % 64 != 0:
+        return False
+    return load_native() is not None
+
+
+_CONV_F32_DEFAULT = "0"
+
+
+def _native_f32_supported(x: torch.Tensor, w: torch.Tensor, stride, padding,
+                          dilation, groups) -> bool:
+    """fp32 operands the conv_f32 kernels serve, FLUXDIST_CONV_F32 aside."""
+    if os.environ.get("FLUXDIST_CONV", "") == "miopen":
+        return False
+    if not (x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32):
         return False
     if groups != 1 or _pair(dilation) != (1, 1):
         return False
@@ -150,6 +182,40 @@ class _FdaConv2d(torch.autograd.Function):
                     gy, x, w, None, list(stride), list(padding), [1, 1],
                     False, [0, 0], 1, [False, True, False])[1]
         return dx, dw, None, None, None
+
+
+class _FdaConv2dF32(torch.autograd.Function):
+    """fp32 forward, input-grad and weight-grad on the conv_f32 kernels. The
+    weight is read as stored by all three ([K][R][S][C], channels_last), and
+    the weight-grad comes back in that memory order, so dw is a view;
+    autograd accumulates it as on the library path."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride, padding):
+        C = require_native("conv_f32_fwd")
+        clear_conv_stats()
+        xc = x.contiguous(memory_format=torch.channels_last)
+        wc = weight.contiguous(memory_format=torch.channels_last)
+        y = C.conv_f32_fwd(xc, wc, *stride, *padding)
+        ctx.save_for_backward(xc, wc)
+        ctx.conf = (stride, padding)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        stride, padding = ctx.conf
+        C = require_native("conv_f32_dgrad")
+        gy = gy.contiguous(memory_format=torch.channels_last)
+        K, Cin, R, S = w.shape
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = C.conv_f32_dgrad(gy, w, x.shape[2], x.shape[3], *stride,
+                                  *padding)
+        if ctx.needs_input_grad[1]:
+            ws = C.conv_f32_wgrad(gy, x, R, S, *stride, *padding)
+            dw = ws.view(K, R, S, Cin).permute(0, 3, 1, 2)
+        return dx, dw, None, None
 
 
 def stem_buffer_key(x, weight, padding):
@@ -274,6 +340,10 @@ def fda_conv2d(x: torch.Tensor, weight: torch.Tensor, stride=(1, 1),
     if _stem_supported(x, weight, stride, padding, dilation, groups):
         return _FdaStemConv2d.apply(x, weight, stride, padding,
                                     _want_conv_stats())
+    if (_native_f32_supported(x, weight, stride, padding, dilation, groups)
+            and (os.environ.get("FLUXDIST_CONV_F32", _CONV_F32_DEFAULT) != "0"
+                 or os.environ.get("FLUXDIST_CONV", "") == "fda")):
+        return _FdaConv2dF32.apply(x, weight, stride, padding)
     if os.environ.get("FLUXDIST_CONV", "") == "fda" and x.is_cuda:
         raise RuntimeError(
             f"FLUXDIST_CONV=fda but shape unsupported by conv_igemm: "

@@ -23,6 +23,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "bn_act.hip"),
         os.path.join(CSRC, "pool.hip"),
         os.path.join(CSRC, "conv_igemm.hip"),
+        os.path.join(CSRC, "conv_f32.hip"),
         os.path.join(CSRC, "preprocess.hip"),
         os.path.join(CSRC, "lars.hip"),
     ],

@@ -6,6 +6,7 @@ with effective TFLOP/s. Run on a GPU box:
     python tools/bench_conv.py [--batch 96] [--iters 50]
     python tools/bench_conv.py --mode dgrad --iters 200   # dgrad arms only
     python tools/bench_conv.py --mode wgrad --iters 200   # wgrad arms only
+    python tools/bench_conv.py --dtype fp32   # conv_f32 kernels vs aten fp32
 """
 
 import argparse
@@ -151,6 +152,63 @@ def wgrad_arms(args):
           f"{tot[1]:22.1f} {tot[2]:22.1f}")
 
 
+def f32_arms(args):
+    """fp32: the conv_f32 kernels against aten's fp32 conv (the library) on
+    the same tensors, per shape and per leg. Device events around --iters
+    calls after warm-up; each figure is the median of --repeats such blocks,
+    the two arms of a leg taken in turn."""
+    C_ = require_native("conv_f32_fwd")
+    torch.backends.cudnn.benchmark = True
+    n = args.batch
+    print(f"# batch={n} fp32, us per call: median of {args.repeats} blocks of "
+          f"{args.iters} calls; tile = conv_f32_config of fwd/dgrad/wgrad")
+    print(f"{'shape':32s} {'fda_fwd':>9s} {'lib_fwd':>9s} | {'fda_dg':>9s} "
+          f"{'lib_dg':>9s} | {'fda_wg':>9s} {'lib_wg':>9s}  fda_TF  tiles (nch)")
+    shapes = SHAPES if args.only < 0 else [SHAPES[args.only]]
+    tot = [0.0] * 6
+    for (c, h, w, k, r, s, cnt) in shapes:
+        pad = r // 2
+        P, Q = (h + 2 * pad - r) // s + 1, (w + 2 * pad - r) // s + 1
+        cl = torch.channels_last
+        x = torch.randn(n, c, h, w, device="cuda").contiguous(memory_format=cl)
+        wt = torch.randn(k, c, r, r, device="cuda").contiguous(memory_format=cl)
+        gy = torch.randn(n, k, P, Q, device="cuda").contiguous(memory_format=cl)
+
+        def lib_bwd(mask):
+            return torch.ops.aten.convolution_backward(
+                gy, x, wt, None, [s, s], [pad, pad], [1, 1], False, [0, 0], 1,
+                mask)
+        arms = [
+            lambda: C_.conv_f32_fwd(x, wt, s, s, pad, pad),
+            lambda: torch.nn.functional.conv2d(x, wt, None, s, pad),
+            lambda: C_.conv_f32_dgrad(gy, wt, h, w, s, s, pad, pad),
+            lambda: lib_bwd([True, False, False]),
+            lambda: C_.conv_f32_wgrad(gy, x, r, r, s, s, pad, pad),
+            lambda: lib_bwd([False, True, False]),
+        ]
+        ts = [[] for _ in arms]
+        for _ in range(args.repeats):
+            for i, fn in enumerate(arms):
+                if args.fda_only and i % 2:
+                    ts[i].append(float("inf"))
+                else:
+                    ts[i].append(event_us(fn, args.iters))
+        med = [sorted(t)[len(t) // 2] for t in ts]
+        for i in range(6):
+            tot[i] += med[i] * cnt
+        rows_d = n * -(-h // s) * -(-w // s)
+        cf = (C_.conv_f32_config(n * P * Q, c, k, r, r, "fwd"),
+              C_.conv_f32_config(rows_d, c, k, r, r, "dgrad"),
+              C_.conv_f32_config(n * P * Q, c, k, r, r, "wgrad"))
+        tf = 2.0 * n * P * Q * k * c * r * r / med[0] / 1e6
+        name = f"{c}x{h}x{w} k{k} {r}x{r} s{s} x{cnt}"
+        print(f"{name:32s} {med[0]:9.1f} {med[1]:9.1f} | {med[2]:9.1f} "
+              f"{med[3]:9.1f} | {med[4]:9.1f} {med[5]:9.1f}  {tf:6.1f}  "
+              f"{cf[0][0]}/{cf[1][0]}/{cf[2][0]} ({cf[2][2]})")
+    print(f"{'TOTAL (weighted by layer count)':32s} {tot[0]:9.1f} {tot[1]:9.1f} "
+          f"| {tot[2]:9.1f} {tot[3]:9.1f} | {tot[4]:9.1f} {tot[5]:9.1f}")
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, default=96)
@@ -166,8 +224,13 @@ def main():
                    help="run only SHAPES[i] (for PMC profiling runs)")
     p.add_argument("--fda-only", action="store_true",
                    help="skip the library arms (clean kernel-trace)")
+    p.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16",
+                   help="fp32: the conv_f32 kernels against aten's fp32 conv, "
+                        "all three legs")
     args = p.parse_args()
     assert torch.cuda.is_available()
+    if args.dtype == "fp32":
+        return f32_arms(args)
     if args.mode == "dgrad":
         return dgrad_arms(args)
     if args.mode == "wgrad":
