@@ -127,7 +127,11 @@ __device__ __forceinline__ float wave_reduce_max(float v) {
 }
 
 // Block-wide reduce for blockDim.x <= 1024 (multiple of 64). `scratch` needs
-// blockDim.x/64 floats. Result broadcast to all threads.
+// blockDim.x/64 floats. Result broadcast to all threads. Every thread has
+// loaded the result before any thread leaves (load, barrier, return), so a
+// caller may start the next reduce on the same scratch at once: without that
+// barrier a fast wave's next partial could land in scratch[0] before a slow
+// wave had read this result.
 __device__ __forceinline__ float block_reduce_sum(float v, float* scratch) {
     const int lane = threadIdx.x & (WAVE - 1);
     const int wid = threadIdx.x / WAVE;
@@ -141,7 +145,9 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* scratch) {
     __syncthreads();
     if (threadIdx.x == 0) scratch[0] = r;
     __syncthreads();
-    return scratch[0];
+    const float out = scratch[0];
+    __syncthreads();
+    return out;
 }
 __device__ __forceinline__ float block_reduce_max(float v, float* scratch) {
     const int lane = threadIdx.x & (WAVE - 1);
@@ -156,7 +162,9 @@ __device__ __forceinline__ float block_reduce_max(float v, float* scratch) {
     __syncthreads();
     if (threadIdx.x == 0) scratch[0] = r;
     __syncthreads();
-    return scratch[0];
+    const float out = scratch[0];
+    __syncthreads();
+    return out;
 }
 
 // V per-channel fp32 accumulators of one thread. A struct, so that the fold
