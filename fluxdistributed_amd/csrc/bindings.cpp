@@ -1107,6 +1107,147 @@ std::tuple<int64_t, int64_t, int64_t, int64_t> conv_f32_config(
     return {p.bm, p.bn, 1, M};
 }
 
+// ---- grouped 3x3 conv (conv_grouped.hip) ----------------------------------
+// Operands: channels_last bf16 activations and the channels_last bf16 weight
+// [K][3][3][cpg] as stored, for all three kernels. Checks in the order of
+// the other conv entry points: dtype, layout, the supported set, sizes, then
+// the device.
+
+// The supported set: groups of cpg = C/g = K/g in {4, 8, 16, 32}, C a
+// multiple of 64, 3x3, padding 1, stride 1 or 2.
+fda::ConvGeom grouped_geometry(const char* op, int64_t N, int64_t C,
+                               int64_t H, int64_t W, int64_t K, int64_t R,
+                               int64_t S, int64_t sy, int64_t sx, int64_t py,
+                               int64_t px, int64_t groups) {
+    TORCH_CHECK(groups >= 1 && C % groups == 0 && K % groups == 0, op,
+                ": groups must divide C and K, got groups=", groups, " C=", C,
+                " K=", K);
+    TORCH_CHECK(C / groups == K / groups, op,
+                ": needs C/g == K/g, got C/g=", C / groups, " K/g=",
+                K / groups);
+    const int64_t cpg = C / groups;
+    TORCH_CHECK(cpg == 4 || cpg == 8 || cpg == 16 || cpg == 32, op,
+                ": channels per group must be 4, 8, 16 or 32, got ", cpg);
+    TORCH_CHECK(R == 3 && S == 3 && py == 1 && px == 1, op,
+                ": needs a 3x3 filter with padding 1, got ", R, "x", S,
+                " padding ", py, "x", px);
+    TORCH_CHECK(sy == sx && (sy == 1 || sy == 2), op,
+                ": stride must be (1,1) or (2,2), got ", sy, "x", sx);
+    return conv_geometry(op, N, C, H, W, K, R, S, sy, sx, py, px);
+}
+
+// w [K, cpg, 3, 3] is the weight of geometry g
+void check_grouped_weight(const char* op, const at::Tensor& w, int64_t K,
+                          int64_t cpg) {
+    TORCH_CHECK(w.size(0) == K && w.size(1) == cpg, op, ": w is [",
+                w.size(0), ", ", w.size(1), ", ..] but the activations and "
+                "groups need [", K, ", ", cpg, ", 3, 3]");
+}
+
+at::Tensor conv_grouped_fwd(at::Tensor x, at::Tensor w, int64_t sy,
+                            int64_t sx, int64_t py, int64_t px,
+                            int64_t groups) {
+    const char* op = "conv_grouped_fwd";
+    check_cl_bf16(op, "x", x);
+    check_cl_bf16(op, "w", w);
+    check_aligned16(op, "x", x);
+    check_aligned16(op, "w", w);
+    const auto g = grouped_geometry(op, x.size(0), x.size(1), x.size(2),
+                                    x.size(3), w.size(0), w.size(2),
+                                    w.size(3), sy, sx, py, px, groups);
+    check_grouped_weight(op, w, g.K, g.C / groups);
+    check_device(op, {x, w});
+    auto y = at::empty({g.N, g.K, g.P, g.Q},
+                       x.options().memory_format(at::MemoryFormat::ChannelsLast));
+    fda::conv_grouped_launch(x.data_ptr(), w.data_ptr(), y.data_ptr(), g,
+                             (int)(g.C / groups), fda::CONV_FWD, cur_stream());
+    return y;
+}
+
+// dy [N,K,P,Q], w [K,cpg,3,3] -> dx [N,C,H,W], every element written
+at::Tensor conv_grouped_dgrad(at::Tensor dy, at::Tensor w, int64_t H,
+                              int64_t W, int64_t sy, int64_t sx, int64_t py,
+                              int64_t px, int64_t groups) {
+    const char* op = "conv_grouped_dgrad";
+    check_cl_bf16(op, "dy", dy);
+    check_cl_bf16(op, "w", w);
+    check_aligned16(op, "dy", dy);
+    check_aligned16(op, "w", w);
+    const auto g = grouped_geometry(op, dy.size(0), w.size(1) * groups, H, W,
+                                    dy.size(1), w.size(2), w.size(3), sy, sx,
+                                    py, px, groups);
+    check_grouped_weight(op, w, g.K, g.C / groups);
+    check_dy(op, dy, g);
+    check_device(op, {dy, w});
+    auto dx = at::empty({g.N, g.C, g.H, g.W},
+                        dy.options().memory_format(at::MemoryFormat::ChannelsLast));
+    fda::conv_grouped_launch(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), g,
+                             (int)(g.C / groups), fda::CONV_DGRAD,
+                             cur_stream());
+    return dx;
+}
+
+// dy [N,K,P,Q], x [N,C,H,W] -> ws [K][9*cpg] fp32: the channels_last weight
+// memory order. More than one chunk: per-chunk slabs and the ordered fold.
+at::Tensor conv_grouped_wgrad(at::Tensor dy, at::Tensor x, int64_t sy,
+                              int64_t sx, int64_t py, int64_t px,
+                              int64_t groups) {
+    const char* op = "conv_grouped_wgrad";
+    check_cl_bf16(op, "dy", dy);
+    check_cl_bf16(op, "x", x);
+    check_aligned16(op, "dy", dy);
+    check_aligned16(op, "x", x);
+    const auto g = grouped_geometry(op, x.size(0), x.size(1), x.size(2),
+                                    x.size(3), dy.size(1), 3, 3, sy, sx, py,
+                                    px, groups);
+    TORCH_CHECK(dy.size(0) == x.size(0), op, ": batch size mismatch: dy has ",
+                dy.size(0), ", x has ", x.size(0));
+    check_dy(op, dy, g);
+    const int cpg = (int)(g.C / groups);
+    const auto p = fda::conv_grouped_plan(g.N, g.H, g.W, g.C, cpg, g.sy,
+                                          fda::CONV_GROUPED_WGRAD);
+    const int64_t n = (int64_t)g.K * 9 * cpg;
+    check_device(op, {dy, x});
+    const auto f32 = x.options().dtype(at::kFloat).memory_format(
+        at::MemoryFormat::Contiguous);
+    auto ws = at::empty({g.K, 9 * cpg}, f32);
+    if (p.nch == 1) {
+        fda::conv_grouped_wgrad_launch(dy.data_ptr(), x.data_ptr(),
+                                       ws.data_ptr<float>(), g, cpg,
+                                       cur_stream());
+        return ws;
+    }
+    auto slab = at::empty({p.nch * n}, f32);
+    fda::conv_grouped_wgrad_launch(dy.data_ptr(), x.data_ptr(),
+                                   slab.data_ptr<float>(), g, cpg,
+                                   cur_stream());
+    fda::wgrad_slab_fold_launch(slab.data_ptr<float>(), p.nch, n,
+                                ws.data_ptr(), false, cur_stream());
+    return ws;
+}
+
+// What the grouped kernels run for x [N,C,H,W]: (th, tw, nch, pixels per
+// chunk). fwd / dgrad: one "chunk", the pixels a block covers with one set
+// of weight registers (images per block x tile). wgrad: nch chunks of whole
+// (image, tile) units.
+std::tuple<int64_t, int64_t, int64_t, int64_t> conv_grouped_config(
+    int64_t N, int64_t H, int64_t W, int64_t C, int64_t groups,
+    int64_t stride, const std::string& mode) {
+    const char* op = "conv_grouped_config";
+    const auto g = grouped_geometry(op, N, C, H, W, C, 3, 3, stride, stride,
+                                    1, 1, groups);
+    TORCH_CHECK(mode == "fwd" || mode == "dgrad" || mode == "wgrad", op,
+                ": mode must be fwd, dgrad or wgrad");
+    const int m = mode == "fwd" ? fda::CONV_GROUPED_FWD
+                  : mode == "dgrad" ? fda::CONV_GROUPED_DGRAD
+                                    : fda::CONV_GROUPED_WGRAD;
+    const auto p = fda::conv_grouped_plan(g.N, g.H, g.W, g.C,
+                                          (int)(C / groups), g.sy, m);
+    const int64_t px = (int64_t)p.th * p.tw;
+    if (m == fda::CONV_GROUPED_WGRAD) return {p.th, p.tw, p.nch, p.upc * px};
+    return {p.th, p.tw, 1, p.ipb * px};
+}
+
 // Operand checks shared by the stem entry points, and their geometry. x8:
 // [N,8,Hp,Wp] channels_last bf16 (spatially pre-padded, channels 3..7
 // zero). Output pixel (p, q) reads filter row r from input row p*sy + r,
@@ -1612,6 +1753,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "fp32 conv weight-grad: per-chunk slabs + ordered fold, no atomics");
     m.def("conv_f32_config", &conv_f32_config,
           "(BM, BN, nch, mch) the fp32 conv kernels run; mode fwd/dgrad/wgrad");
+    m.def("conv_grouped_fwd", &conv_grouped_fwd,
+          "grouped 3x3 conv forward (NHWC bf16, cpg 4/8/16/32, weights in "
+          "registers, input staged once)");
+    m.def("conv_grouped_dgrad", &conv_grouped_dgrad,
+          "grouped 3x3 conv input-grad from the weight as stored");
+    m.def("conv_grouped_wgrad", &conv_grouped_wgrad,
+          "grouped 3x3 conv weight-grad [K][9*cpg] fp32: per-chunk slabs + "
+          "ordered fold, no atomics");
+    m.def("conv_grouped_config", &conv_grouped_config,
+          "(th, tw, nch, pixels per chunk) the grouped conv kernels run; "
+          "mode fwd/dgrad/wgrad");
     m.def("conv_igemm_dgrad", &conv_igemm_dgrad,
           "implicit-GEMM conv input-grad (NHWC bf16, MFMA; optional fused "
           "+= accum epilogue)",

@@ -319,6 +319,35 @@ WgradF32Plan conv_f32_wgrad_plan(long M, int C, int K, int R, int S);
 void conv_f32_wgrad_launch(const float* dy, const float* x, float* ws,
                            const ConvGeom& g, hipStream_t stream);
 
+// Grouped 3x3 conv, NHWC bf16 (conv_grouped.hip): groups of cpg = C/g = K/g
+// in {4, 8, 16, 32} channels, padding 1, stride 1 or 2. The geometry is a
+// ConvGeom with K == C, R == S == 3; the weight is always w [K][3][3][cpg]
+// as stored.
+// What a launch runs: a th x tw spatial tile (tiles_h x tiles_w of them per
+// image; for a stride-2 dgrad per parity class) x a 64-channel slab per
+// block. fwd / dgrad: ipb images per block. wgrad: nch chunks of upc
+// (image, tile) units each. blocks: the grid; lds_bytes: dynamic LDS.
+constexpr int CONV_GROUPED_FWD = 0;
+constexpr int CONV_GROUPED_DGRAD = 1;
+constexpr int CONV_GROUPED_WGRAD = 2;
+struct ConvGroupedPlan {
+    int th, tw, tiles_h, tiles_w, classes, ipb, nch, upc;
+    long blocks;
+    size_t lds_bytes;
+};
+ConvGroupedPlan conv_grouped_plan(int N, int H, int W, int C, int cpg,
+                                  int stride, int mode);
+// fwd:   src=x [N,H,W,C],  out=y [N,P,Q,C]
+// dgrad: src=dy [N,P,Q,C], out=dx [N,H,W,C], every element written
+void conv_grouped_launch(const void* src, const void* w, void* out,
+                         const ConvGeom& g, int cpg, ConvMode mode,
+                         hipStream_t stream);
+// plan.nch == 1: ws is the result [K][9*cpg] fp32. nch > 1: ws is
+// [nch][K][9*cpg], chunk c stores into slab c and wgrad_slab_fold_launch
+// sums them. Every element is written exactly once either way.
+void conv_grouped_wgrad_launch(const void* dy, const void* x, float* ws,
+                               const ConvGeom& g, int cpg, hipStream_t stream);
+
 // batched conv-weight transpose: w[k][rc] -> wt[rc][k] for all tensors in
 // one launch (device pointer arrays)
 void wt_transpose_launch(const long* src_ptrs, long* dst_ptrs, const int* Ks,

@@ -5,5 +5,8 @@ from .resnet import (  # noqa: F401
     resnet50,
     resnet101,
     resnet152,
+    resnext50_32x4d,
+    resnext101_32x4d,
+    resnext101_64x4d,
     build_model,
 )

@@ -1,4 +1,5 @@
-"""ResNet family (18/34/50/101/152), written from scratch for this framework.
+"""ResNet family (18/34/50/101/152) and ResNeXt (50 32x4d, 101 32x4d,
+101 64x4d), written from scratch for this framework.
 
 Parity: the reference trains Metalhead ResNets — ResNet-34 flagship
 (/root/reference/README.md:27), ResNet-50 in the process path
@@ -98,8 +99,9 @@ def _junction_fusible(x: torch.Tensor, conv: nn.Conv2d) -> bool:
                              conv.dilation, conv.groups)
 
 
-def conv3x3(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
-    return FdaConv2d(cin, cout, 3, stride=stride, padding=1, bias=False)
+def conv3x3(cin: int, cout: int, stride: int = 1, groups: int = 1) -> nn.Conv2d:
+    return FdaConv2d(cin, cout, 3, stride=stride, padding=1, groups=groups,
+                     bias=False)
 
 
 def conv1x1(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
@@ -135,13 +137,17 @@ class Bottleneck(nn.Module):
     expansion = 4
 
     def __init__(self, cin: int, cout: int, stride: int = 1,
-                 downsample: Optional[nn.Module] = None):
+                 downsample: Optional[nn.Module] = None, groups: int = 1,
+                 base_width: int = 64):
         super().__init__()
-        self.conv1 = conv1x1(cin, cout)
-        self.bn1 = FusedBNAct(cout, relu=True)
-        self.conv2 = conv3x3(cout, cout, stride)
-        self.bn2 = FusedBNAct(cout, relu=True)
-        self.conv3 = conv1x1(cout, cout * self.expansion)
+        # ResNeXt: the 3x3 conv is grouped and the inner width scales with
+        # base_width; groups=1, base_width=64 is the plain bottleneck
+        width = int(cout * base_width / 64) * groups
+        self.conv1 = conv1x1(cin, width)
+        self.bn1 = FusedBNAct(width, relu=True)
+        self.conv2 = conv3x3(width, width, stride, groups)
+        self.bn2 = FusedBNAct(width, relu=True)
+        self.conv3 = conv1x1(width, cout * self.expansion)
         self.bn3 = FusedBNAct(cout * self.expansion, relu=True)
         self.downsample = downsample
 
@@ -171,9 +177,15 @@ class Downsample(nn.Module):
 
 class ResNet(nn.Module):
     def __init__(self, block: Type[nn.Module], layers: List[int],
-                 num_classes: int = 1000, small_input: bool = False):
+                 num_classes: int = 1000, small_input: bool = False,
+                 groups: int = 1, width_per_group: int = 64):
         super().__init__()
+        if (groups, width_per_group) != (1, 64) and block is not Bottleneck:
+            raise ValueError("groups / width_per_group need Bottleneck blocks")
         self.small_input = small_input
+        # extra block arguments: none for the plain ResNets
+        self._block_kw = ({} if (groups, width_per_group) == (1, 64) else
+                          dict(groups=groups, base_width=width_per_group))
         self.cin = 64
         if small_input:  # CIFAR-style stem (BASELINE config 1)
             self.conv1 = FdaConv2d(3, 64, 3, stride=1, padding=1, bias=False)
@@ -194,9 +206,10 @@ class ResNet(nn.Module):
         downsample = None
         if stride != 1 or self.cin != cout * block.expansion:
             downsample = Downsample(self.cin, cout * block.expansion, stride)
-        blocks = [block(self.cin, cout, stride, downsample)]
+        kw = self._block_kw
+        blocks = [block(self.cin, cout, stride, downsample, **kw)]
         self.cin = cout * block.expansion
-        blocks += [block(self.cin, cout) for _ in range(n - 1)]
+        blocks += [block(self.cin, cout, **kw) for _ in range(n - 1)]
         return nn.Sequential(*blocks)
 
     def _init_weights(self):
@@ -252,12 +265,27 @@ def resnet152(**kw):
     return ResNet(Bottleneck, [3, 8, 36, 3], **kw)
 
 
+def resnext50_32x4d(**kw):
+    return ResNet(Bottleneck, [3, 4, 6, 3], groups=32, width_per_group=4, **kw)
+
+
+def resnext101_32x4d(**kw):
+    return ResNet(Bottleneck, [3, 4, 23, 3], groups=32, width_per_group=4, **kw)
+
+
+def resnext101_64x4d(**kw):
+    return ResNet(Bottleneck, [3, 4, 23, 3], groups=64, width_per_group=4, **kw)
+
+
 _ZOO = {
     "resnet18": resnet18,
     "resnet34": resnet34,
     "resnet50": resnet50,
     "resnet101": resnet101,
     "resnet152": resnet152,
+    "resnext50_32x4d": resnext50_32x4d,
+    "resnext101_32x4d": resnext101_32x4d,
+    "resnext101_64x4d": resnext101_64x4d,
 }
 
 

@@ -7,8 +7,16 @@ v_mfma_f32_16x16x32_bf16 tiles, LDS-staged via global_load_lds. Supported
 there: NHWC bf16, dilation 1, groups 1, C and K multiples of 64 (all
 ResNet body convs) — fwd, dgrad AND wgrad. Small-C stems (C<=5, e.g. the
 ImageNet 7x7 and CIFAR 3x3 stems) run on the dedicated CONV_STEM kernels;
-only genuinely unsupported shapes (grouped/dilated, odd channel counts)
-fall back to the library path.
+only genuinely unsupported shapes (dilated, odd channel counts, grouped
+convs outside the set below) fall back to the library path.
+
+Grouped 3x3 convs (the ResNeXt bottlenecks) have kernels of their own,
+csrc/conv_grouped.hip: bf16, padding 1, stride 1 or 2, C/g == K/g in
+{4, 8, 16, 32}, C a multiple of 64; forward, dgrad and wgrad read the weight
+as stored and keep it in registers. Plain autograd like the fp32 path. On by
+default (FLUXDIST_CONV_GROUPED=1): against the library's grouped conv it is
+faster on every ResNeXt-50 shape and leg and the ResNeXt-50 step is 1.58x
+faster (profiles/conv_grouped.md).
 
 fp32 operands have a native path of their own, csrc/conv_f32.hip on the
 fp32 MFMA (v_mfma_f32_16x16x4_f32): the same constraints (NHWC, dilation 1,
@@ -26,6 +34,10 @@ Env:
                          native path supports)
   FLUXDIST_CONV_F32=1|0  fp32 body convs on conv_f32.hip (1) or the library
                          (0, the default). Read at call time. FLUXDIST_CONV=fda
+                         implies 1.
+  FLUXDIST_CONV_GROUPED=1|0  grouped 3x3 convs on conv_grouped.hip (1, the
+                         default) or the library (0). Read at call time.
+                         FLUXDIST_CONV=miopen overrides it, FLUXDIST_CONV=fda
                          implies 1.
   FLUXDIST_WGRAD_SLAB=0  weight-grads into flat G: atomic workspace + queued
                          flush for every shape (default 1: slabs + ordered
@@ -81,6 +93,30 @@ def _native_f32_supported(x: torch.Tensor, w: torch.Tensor, stride, padding,
         return False
     C, K = x.shape[1], w.shape[0]
     if C % 64 != 0 or K % 64 != 0:
+        return False
+    return load_native() is not None
+
+
+_CONV_GROUPED_DEFAULT = "1"
+
+
+def _native_grouped_supported(x: torch.Tensor, w: torch.Tensor, stride,
+                              padding, dilation, groups) -> bool:
+    """Grouped 3x3 convs the conv_grouped kernels serve, FLUXDIST_CONV_GROUPED
+    aside: bf16, padding 1, stride 1 or 2, C/g == K/g in {4, 8, 16, 32},
+    C a multiple of 64."""
+    if os.environ.get("FLUXDIST_CONV", "") == "miopen":
+        return False
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16):
+        return False
+    if groups == 1 or _pair(dilation) != (1, 1) or _pair(padding) != (1, 1):
+        return False
+    if _pair(stride) not in ((1, 1), (2, 2)) or tuple(w.shape[2:]) != (3, 3):
+        return False
+    C, K = x.shape[1], w.shape[0]
+    if C != K or C % 64 != 0 or C % groups != 0:
+        return False
+    if C // groups not in (4, 8, 16, 32):
         return False
     return load_native() is not None
 
@@ -218,6 +254,42 @@ class _FdaConv2dF32(torch.autograd.Function):
         return dx, dw, None, None
 
 
+class _FdaConv2dGrouped(torch.autograd.Function):
+    """Grouped 3x3 forward, input-grad and weight-grad on the conv_grouped
+    kernels. All three read the weight as stored ([K][3][3][cpg],
+    channels_last); the weight-grad comes back fp32 in that memory order and
+    is cast once. Plain autograd: no conv->BN stats, no arenas, no direct
+    write into flat G."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride, groups):
+        C = require_native("conv_grouped_fwd")
+        clear_conv_stats()
+        xc = x.contiguous(memory_format=torch.channels_last)
+        wc = weight.contiguous(memory_format=torch.channels_last)
+        y = C.conv_grouped_fwd(xc, wc, *stride, 1, 1, groups)
+        ctx.save_for_backward(xc, wc)
+        ctx.conf = (stride, groups)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        stride, groups = ctx.conf
+        C = require_native("conv_grouped_dgrad")
+        gy = gy.contiguous(memory_format=torch.channels_last)
+        K, cpg = w.shape[0], w.shape[1]
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = C.conv_grouped_dgrad(gy, w, x.shape[2], x.shape[3], *stride,
+                                      1, 1, groups)
+        if ctx.needs_input_grad[1]:
+            ws = C.conv_grouped_wgrad(gy, x, *stride, 1, 1, groups)
+            dw = (ws.to(torch.bfloat16).view(K, 3, 3, cpg)
+                  .permute(0, 3, 1, 2))
+        return dx, dw, None, None
+
+
 def stem_buffer_key(x, weight, padding):
     """What a padded stem input buffer is reused by: its shape and device."""
     N, _, H, W = x.shape
@@ -344,6 +416,11 @@ def fda_conv2d(x: torch.Tensor, weight: torch.Tensor, stride=(1, 1),
             and (os.environ.get("FLUXDIST_CONV_F32", _CONV_F32_DEFAULT) != "0"
                  or os.environ.get("FLUXDIST_CONV", "") == "fda")):
         return _FdaConv2dF32.apply(x, weight, stride, padding)
+    if (_native_grouped_supported(x, weight, stride, padding, dilation, groups)
+            and (os.environ.get("FLUXDIST_CONV_GROUPED",
+                                _CONV_GROUPED_DEFAULT) != "0"
+                 or os.environ.get("FLUXDIST_CONV", "") == "fda")):
+        return _FdaConv2dGrouped.apply(x, weight, stride, groups)
     if os.environ.get("FLUXDIST_CONV", "") == "fda" and x.is_cuda:
         raise RuntimeError(
             f"FLUXDIST_CONV=fda but shape unsupported by conv_igemm: "

@@ -7,6 +7,7 @@ with effective TFLOP/s. Run on a GPU box:
     python tools/bench_conv.py --mode dgrad --iters 200   # dgrad arms only
     python tools/bench_conv.py --mode wgrad --iters 200   # wgrad arms only
     python tools/bench_conv.py --dtype fp32   # conv_f32 kernels vs aten fp32
+    python tools/bench_conv.py --groups       # conv_grouped vs the library
 """
 
 import argparse
@@ -209,6 +210,79 @@ def f32_arms(args):
           f"| {tot[2]:9.1f} {tot[3]:9.1f} | {tot[4]:9.1f} {tot[5]:9.1f}")
 
 
+# grouped 3x3 convs of ResNeXt-50 32x4d: (C, H, W, groups, stride, count)
+GROUPED_SHAPES = [
+    (128, 56, 56, 32, 1, 3),
+    (256, 56, 56, 32, 2, 1),
+    (256, 28, 28, 32, 1, 3),
+    (512, 28, 28, 32, 2, 1),
+    (512, 14, 14, 32, 1, 5),
+    (1024, 14, 14, 32, 2, 1),
+    (1024, 7, 7, 32, 1, 2),
+]
+HBM_BYTES_PER_US = 8.0e6   # MI355X peak, 8 TB/s
+
+
+def grouped_arms(args):
+    """Grouped 3x3: the conv_grouped kernels against the library's grouped
+    conv on the same tensors, per shape and per leg; figures as for --dtype
+    fp32. floor: the time the leg's compulsory bytes (input + output once;
+    wgrad: x + dy once) take at the peak HBM rate, and the fraction of it
+    the native kernel reaches."""
+    C_ = require_native("conv_grouped_fwd")
+    torch.backends.cudnn.benchmark = True
+    n = args.batch
+    print(f"# batch={n} grouped bf16, us per call: median of {args.repeats} "
+          f"blocks of {args.iters} calls; floor at 8 TB/s")
+    print(f"{'shape':30s} {'fda_fwd':>8s} {'lib_fwd':>8s} | {'fda_dg':>8s} "
+          f"{'lib_dg':>8s} | {'fda_wg':>8s} {'lib_wg':>8s} | {'floor':>6s}  "
+          f"fwd/dg/wg of floor  wgrad (nch, px)")
+    shapes = (GROUPED_SHAPES if args.only < 0
+              else [GROUPED_SHAPES[args.only]])
+    tot = [0.0] * 6
+    cl = torch.channels_last
+    for (c, h, w, g, s, cnt) in shapes:
+        P, Q = (h - 1) // s + 1, (w - 1) // s + 1
+        x = torch.randn(n, c, h, w, device="cuda").bfloat16() \
+            .contiguous(memory_format=cl)
+        wt = torch.randn(c, c // g, 3, 3, device="cuda").bfloat16() \
+            .contiguous(memory_format=cl)
+        gy = torch.randn(n, c, P, Q, device="cuda").bfloat16() \
+            .contiguous(memory_format=cl)
+
+        def lib_bwd(mask):
+            return torch.ops.aten.convolution_backward(
+                gy, x, wt, None, [s, s], [1, 1], [1, 1], False, [0, 0], g,
+                mask)
+        arms = [
+            lambda: C_.conv_grouped_fwd(x, wt, s, s, 1, 1, g),
+            lambda: torch.nn.functional.conv2d(x, wt, None, s, 1, 1, g),
+            lambda: C_.conv_grouped_dgrad(gy, wt, h, w, s, s, 1, 1, g),
+            lambda: lib_bwd([True, False, False]),
+            lambda: C_.conv_grouped_wgrad(gy, x, s, s, 1, 1, g),
+            lambda: lib_bwd([False, True, False]),
+        ]
+        ts = [[] for _ in arms]
+        for _ in range(args.repeats):
+            for i, fn in enumerate(arms):
+                if args.fda_only and i % 2:
+                    ts[i].append(float("inf"))
+                else:
+                    ts[i].append(event_us(fn, args.iters))
+        med = [sorted(t)[len(t) // 2] for t in ts]
+        for i in range(6):
+            tot[i] += med[i] * cnt
+        floor = 2.0 * (x.numel() + gy.numel()) / HBM_BYTES_PER_US
+        cf = C_.conv_grouped_config(n, h, w, c, g, s, "wgrad")
+        name = f"{c}x{h}x{w} g{g} s{s} x{cnt}"
+        print(f"{name:30s} {med[0]:8.1f} {med[1]:8.1f} | {med[2]:8.1f} "
+              f"{med[3]:8.1f} | {med[4]:8.1f} {med[5]:8.1f} | {floor:6.1f}  "
+              f"{floor / med[0]:.2f}/{floor / med[2]:.2f}/{floor / med[4]:.2f}"
+              f"  ({cf[2]}, {cf[3]})", flush=True)
+    print(f"{'TOTAL (weighted by layer count)':30s} {tot[0]:8.1f} {tot[1]:8.1f} "
+          f"| {tot[2]:8.1f} {tot[3]:8.1f} | {tot[4]:8.1f} {tot[5]:8.1f}")
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, default=96)
@@ -227,8 +301,14 @@ def main():
     p.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16",
                    help="fp32: the conv_f32 kernels against aten's fp32 conv, "
                         "all three legs")
+    p.add_argument("--groups", action="store_true",
+                   help="the grouped 3x3 shapes of ResNeXt-50 32x4d: the "
+                        "conv_grouped kernels against the library, all three "
+                        "legs")
     args = p.parse_args()
     assert torch.cuda.is_available()
+    if args.groups:
+        return grouped_arms(args)
     if args.dtype == "fp32":
         return f32_arms(args)
     if args.mode == "dgrad":
