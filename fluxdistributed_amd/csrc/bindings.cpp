@@ -1248,6 +1248,123 @@ std::tuple<int64_t, int64_t, int64_t, int64_t> conv_grouped_config(
     return {p.th, p.tw, 1, p.ipb * px};
 }
 
+// ---- squeeze-and-excitation (se.hip) ---------------------------------------
+// u, identity, out, gout: channels_last bf16 [N,C,H,W]. w1 [Cr,C], b1 [Cr],
+// w2 [C,Cr], b2 [C]: contiguous bf16. s, z [N,C] and h [N,Cr]: fp32.
+
+void check_se_channels(const char* op, int64_t C, int64_t Cr) {
+    TORCH_CHECK(C % 64 == 0 && C >= 64 && C <= 2048, op,
+                ": C must be a multiple of 64 in [64, 2048], got ", C);
+    TORCH_CHECK(Cr % 4 == 0 && Cr >= 4 && Cr <= 128, op,
+                ": Cr must be a multiple of 4 in [4, 128], got ", Cr);
+}
+
+// returns Cr
+int64_t check_se_weights(const char* op, const at::Tensor& w1,
+                         const at::Tensor& w2, int64_t C) {
+    TORCH_CHECK(w1.dim() == 2 && w2.dim() == 2, op,
+                ": w1 and w2 must be 2-D");
+    const int64_t Cr = w1.size(0);
+    check_se_channels(op, C, Cr);
+    TORCH_CHECK(w1.size(1) == C && w2.size(0) == C && w2.size(1) == Cr, op,
+                ": need w1 [Cr, C] and w2 [C, Cr] with C=", C, ", got w1 [",
+                w1.size(0), ", ", w1.size(1), "] w2 [", w2.size(0), ", ",
+                w2.size(1), "]");
+    check_flat(op, "w1", w1, at::kBFloat16, Cr * C);
+    check_flat(op, "w2", w2, at::kBFloat16, C * Cr);
+    check_aligned16(op, "w1", w1);
+    check_aligned16(op, "w2", w2);
+    return Cr;
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> se_fwd(
+    at::Tensor u, at::Tensor identity, at::Tensor w1, at::Tensor b1,
+    at::Tensor w2, at::Tensor b2) {
+    const char* op = "se_fwd";
+    check_cl_bf16(op, "u", u);
+    check_like(op, "identity", identity, u, "u");
+    check_aligned16(op, "u", u);
+    check_aligned16(op, "identity", identity);
+    const int64_t N = u.size(0), C = u.size(1), HW = u.size(2) * u.size(3);
+    TORCH_CHECK(N >= 1 && N <= 65535 && HW >= 1, op,
+                ": need 1 <= N <= 65535 and a non-empty image");
+    const int64_t Cr = check_se_weights(op, w1, w2, C);
+    check_flat(op, "b1", b1, at::kBFloat16, Cr);
+    check_flat(op, "b2", b2, at::kBFloat16, C);
+    check_device(op, {u, identity, w1, b1, w2, b2});
+    const auto p = fda::se_plan((int)N, (int)HW, (int)C);
+    const auto f32 = u.options().dtype(at::kFloat).memory_format(
+        at::MemoryFormat::Contiguous);
+    auto out = at::empty_like(u);
+    auto s = at::empty({N, C}, f32);
+    auto h = at::empty({N, Cr}, f32);
+    auto z = at::empty({N, C}, f32);
+    auto part = at::empty({N, p.nsplit, C}, f32);
+    fda::se_fwd_launch(u.data_ptr(), identity.data_ptr(), w1.data_ptr(),
+                       b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                       out.data_ptr(), s.data_ptr<float>(),
+                       h.data_ptr<float>(), z.data_ptr<float>(),
+                       part.data_ptr<float>(), (int)N, (int)HW, (int)C,
+                       (int)Cr, cur_stream());
+    return {out, s, h, z};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
+           at::Tensor>
+se_bwd(at::Tensor gout, at::Tensor out, at::Tensor u, at::Tensor s,
+       at::Tensor h, at::Tensor z, at::Tensor w1, at::Tensor w2) {
+    const char* op = "se_bwd";
+    check_cl_bf16(op, "u", u);
+    check_like(op, "out", out, u, "u");
+    check_like(op, "gout", gout, u, "u");
+    check_aligned16(op, "u", u);
+    check_aligned16(op, "out", out);
+    check_aligned16(op, "gout", gout);
+    const int64_t N = u.size(0), C = u.size(1), HW = u.size(2) * u.size(3);
+    TORCH_CHECK(N >= 1 && N <= 65535 && HW >= 1, op,
+                ": need 1 <= N <= 65535 and a non-empty image");
+    const int64_t Cr = check_se_weights(op, w1, w2, C);
+    check_flat(op, "s", s, at::kFloat, N * C);
+    check_flat(op, "h", h, at::kFloat, N * Cr);
+    check_flat(op, "z", z, at::kFloat, N * C);
+    check_device(op, {gout, out, u, s, h, z, w1, w2});
+    const auto p = fda::se_plan((int)N, (int)HW, (int)C);
+    const auto f32 = u.options().dtype(at::kFloat).memory_format(
+        at::MemoryFormat::Contiguous);
+    const auto bf = w1.options();
+    auto du = at::empty_like(u);
+    auto gid = at::empty_like(u);
+    auto dw1 = at::empty({Cr, C}, bf);
+    auto db1 = at::empty({Cr}, bf);
+    auto dw2 = at::empty({C, Cr}, bf);
+    auto db2 = at::empty({C}, bf);
+    auto part = at::empty({N, p.nsplit, C}, f32);
+    auto da2 = at::empty({N, C}, f32);
+    auto da1 = at::empty({N, Cr}, f32);
+    auto dzs = at::empty({N, C}, f32);
+    fda::se_bwd_launch(gout.data_ptr(), out.data_ptr(), u.data_ptr(),
+                       s.data_ptr<float>(), h.data_ptr<float>(),
+                       z.data_ptr<float>(), w1.data_ptr(), w2.data_ptr(),
+                       du.data_ptr(), gid.data_ptr(), dw1.data_ptr(),
+                       db1.data_ptr(), dw2.data_ptr(), db2.data_ptr(),
+                       part.data_ptr<float>(), da2.data_ptr<float>(),
+                       da1.data_ptr<float>(), dzs.data_ptr<float>(), (int)N,
+                       (int)HW, (int)C, (int)Cr, cur_stream());
+    return {du, gid, dw1, db1, dw2, db2};
+}
+
+// What the SE kernels run for [N, C, HW] with Cr hidden units: (nsplit, rows
+// per chunk, images per excite block).
+std::tuple<int64_t, int64_t, int64_t> se_config(int64_t N, int64_t HW,
+                                                int64_t C, int64_t Cr) {
+    const char* op = "se_config";
+    check_se_channels(op, C, Cr);
+    TORCH_CHECK(N >= 1 && N <= 65535 && HW >= 1 && HW <= (1 << 24), op,
+                ": need 1 <= N <= 65535 and 1 <= HW <= 2^24");
+    const auto p = fda::se_plan((int)N, (int)HW, (int)C);
+    return {p.nsplit, p.rpc, p.ipb};
+}
+
 // Operand checks shared by the stem entry points, and their geometry. x8:
 // [N,8,Hp,Wp] channels_last bf16 (spatially pre-padded, channels 3..7
 // zero). Output pixel (p, q) reads filter row r from input row p*sy + r,
@@ -1764,6 +1881,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("conv_grouped_config", &conv_grouped_config,
           "(th, tw, nch, pixels per chunk) the grouped conv kernels run; "
           "mode fwd/dgrad/wgrad");
+    m.def("se_fwd", &se_fwd,
+          "squeeze-and-excitation tail: (out, s, h, z) = relu(u * s + "
+          "identity) with the fp32 gate and its saved intermediates");
+    m.def("se_bwd", &se_bwd,
+          "squeeze-and-excitation backward: (du, gidentity, dw1, db1, dw2, "
+          "db2)");
+    m.def("se_config", &se_config,
+          "(nsplit, rows per chunk, images per excite block) the SE kernels "
+          "run");
     m.def("conv_igemm_dgrad", &conv_igemm_dgrad,
           "implicit-GEMM conv input-grad (NHWC bf16, MFMA; optional fused "
           "+= accum epilogue)",

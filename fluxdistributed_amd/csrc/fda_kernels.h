@@ -348,6 +348,32 @@ void conv_grouped_launch(const void* src, const void* w, void* out,
 void conv_grouped_wgrad_launch(const void* dy, const void* x, float* ws,
                                const ConvGeom& g, int cpg, hipStream_t stream);
 
+// Squeeze-and-Excitation block tail (se.hip), NHWC bf16 activations:
+//   out = relu(u * s[n][c] + identity), s = sigmoid(W2 relu(W1 mean_hw(u) +
+//   b1) + b2). C % 64 == 0, 64 <= C <= 2048; Cr % 4 == 0, 4 <= Cr <= 128.
+// w1 [Cr][C], b1 [Cr], w2 [C][Cr], b2 [C]: bf16 as nn.Linear stores them.
+// s, z [N][C] and h [N][Cr] are fp32.
+// What a launch runs: HW is cut into nsplit chunks of rpc rows (the last may
+// be short) for the reductions and the streaming passes, grid (nsplit, N);
+// the excite kernels serve ipb images per block.
+struct SePlan {
+    int nsplit, rpc, ipb;
+};
+SePlan se_plan(int N, int HW, int C);
+// part: [N][nsplit][C] fp32 workspace, every element written (no pre-zero)
+void se_fwd_launch(const void* u, const void* identity, const void* w1,
+                   const void* b1, const void* w2, const void* b2, void* out,
+                   float* s, float* h, float* z, float* part, int N, int HW,
+                   int C, int Cr, hipStream_t st);
+// du, gidentity like u; dw1/db1/dw2/db2 bf16 in the parameters' layouts.
+// Workspaces: part as above, da2 and dzs [N][C], da1 [N][Cr], all fp32.
+void se_bwd_launch(const void* gout, const void* out, const void* u,
+                   const float* s, const float* h, const float* z,
+                   const void* w1, const void* w2, void* du, void* gidentity,
+                   void* dw1, void* db1, void* dw2, void* db2, float* part,
+                   float* da2, float* da1, float* dzs, int N, int HW, int C,
+                   int Cr, hipStream_t st);
+
 // batched conv-weight transpose: w[k][rc] -> wt[rc][k] for all tensors in
 // one launch (device pointer arrays)
 void wt_transpose_launch(const long* src_ptrs, long* dst_ptrs, const int* Ks,

@@ -12,6 +12,10 @@ and read back for a separate BN pass; block tails take the shortcut as the
 `residual` operand. scale/shift of ALL layers come from one batched fold
 launch (`bn_fold_eval_batch`) into a flat fp32 arena.
 
+A squeeze-and-excitation block's last pair has neither ReLU nor residual (it
+fuses like a shortcut pair); its output and the shortcut then go through the
+block's own SE op (ops/se.py), the same one `model.eval()` runs.
+
 Wherever the native kernels do not apply (CPU, fp32, FLUXDIST_CONV=miopen,
 unsupported channel counts) or with FLUXDIST_INFER_FUSE=0, a pair runs the
 model's own ops (`fda_conv2d`, then `batch_norm_act(training=False)`), and
@@ -28,7 +32,7 @@ import torch
 import torch.nn as nn
 
 from .models.resnet import (BasicBlock, Bottleneck, Downsample, FusedBNAct,
-                            ResNet)
+                            ResNet, SqueezeExcite)
 from .ops.conv import (FdaConv2d, _native_supported, _stem_supported,
                        fda_conv2d, pack_stem_operands, stem_buffer_key)
 from .ops.functional import (GlobalAvgPool, MaxPool2d, batch_norm_act,
@@ -66,10 +70,10 @@ class _Pair:
 
 
 class _Block:
-    __slots__ = ("pairs", "down")
+    __slots__ = ("pairs", "down", "se")
 
-    def __init__(self, pairs, down):
-        self.pairs, self.down = pairs, down
+    def __init__(self, pairs, down, se=None):
+        self.pairs, self.down, self.se = pairs, down, se
 
 
 class _FoldArena:
@@ -196,10 +200,19 @@ class InferenceModel:
                     raise TypeError(
                         f"compile_for_inference: unrecognised block "
                         f"{type(blk).__name__}")
-                if not all(p.bn.relu for p in body):
+                se = blk.__dict__["_modules"].get("se")
+                if se is not None:
+                    if type(se) is not SqueezeExcite:
+                        raise TypeError(
+                            f"compile_for_inference: unrecognised gate "
+                            f"{type(se).__name__}")
+                    claimed.add(id(se))
+                # an SE block's last BN feeds the SE op: no ReLU of its own
+                if not (all(p.bn.relu for p in body[:-1])
+                        and body[-1].bn.relu == (se is None)):
                     raise TypeError("compile_for_inference: block BN without "
                                     "ReLU")
-                self.blocks.append(_Block(body, down))
+                self.blocks.append(_Block(body, down, se))
 
         # nothing the walk did not pair may remain: a module this code does
         # not know would otherwise be dropped from the forward silently
@@ -331,6 +344,10 @@ class InferenceModel:
                 out = x
                 for p in blk.pairs[:-1]:
                     out = self._run_pair(p, out, fuse=fuse)
+                if blk.se is not None:
+                    x = blk.se(self._run_pair(blk.pairs[-1], out, fuse=fuse),
+                               identity)
+                    continue
                 x = self._run_pair(blk.pairs[-1], out, residual=identity,
                                    fuse=fuse)
             return self.model.fc(self.model.avgpool(x))

@@ -1,5 +1,6 @@
-"""ResNet family (18/34/50/101/152) and ResNeXt (50 32x4d, 101 32x4d,
-101 64x4d), written from scratch for this framework.
+"""ResNet family (18/34/50/101/152), ResNeXt (50 32x4d, 101 32x4d,
+101 64x4d) and their squeeze-and-excitation variants (SE-ResNet 18..152,
+SE-ResNeXt 50/101 32x4d), written from scratch for this framework.
 
 Parity: the reference trains Metalhead ResNets — ResNet-34 flagship
 (/root/reference/README.md:27), ResNet-50 in the process path
@@ -18,6 +19,7 @@ import torch.nn as nn
 
 from ..ops.conv import FdaConv2d, _native_supported
 from ..ops.linear import FdaLinear
+from ..ops.se import se_scale_add_relu
 from ..ops.functional import (batch_norm_act, batch_norm_act_pool,
                               bn_act_pool_fusible, MaxPool2d, GlobalAvgPool)
 
@@ -108,19 +110,61 @@ def conv1x1(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
     return FdaConv2d(cin, cout, 1, stride=stride, bias=False)
 
 
+class SqueezeExcite(nn.Module):
+    """The gate of a squeeze-and-excitation block (Hu et al. 2018): two
+    dense layers C -> C/reduction -> C over the per-image channel means.
+    Holds the parameters in the nn.Linear layouts with nn.Linear's default
+    initialisation; forward(u, identity) is the whole block tail,
+    relu(u * sigmoid(W2 relu(W1 mean_hw(u) + b1) + b2) + identity), one
+    native op on the GPU (ops/se.py)."""
+
+    def __init__(self, channels: int, reduction: int = 16):
+        super().__init__()
+        hidden = channels // reduction
+        if hidden < 1:
+            raise ValueError(f"SqueezeExcite: {channels} channels cannot be "
+                             f"reduced by {reduction}")
+        self.channels, self.hidden = channels, hidden
+        self.w1 = nn.Parameter(torch.empty(hidden, channels))
+        self.b1 = nn.Parameter(torch.empty(hidden))
+        self.w2 = nn.Parameter(torch.empty(channels, hidden))
+        self.b2 = nn.Parameter(torch.empty(channels))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        # nn.Linear.reset_parameters: U(-1/sqrt(fan_in), 1/sqrt(fan_in)) for
+        # the weight (kaiming_uniform, a = sqrt(5)) and for the bias
+        for w, b in ((self.w1, self.b1), (self.w2, self.b2)):
+            bound = w.shape[1] ** -0.5
+            nn.init.uniform_(w, -bound, bound)
+            nn.init.uniform_(b, -bound, bound)
+
+    def forward(self, u, identity):
+        return se_scale_add_relu(u, identity, self.w1, self.b1, self.w2,
+                                 self.b2)
+
+
 class BasicBlock(nn.Module):
     expansion = 1
 
     def __init__(self, cin: int, cout: int, stride: int = 1,
-                 downsample: Optional[nn.Module] = None):
+                 downsample: Optional[nn.Module] = None, se: bool = False):
         super().__init__()
         self.conv1 = conv3x3(cin, cout, stride)
         self.bn1 = FusedBNAct(cout, relu=True)
         self.conv2 = conv3x3(cout, cout)
-        self.bn2 = FusedBNAct(cout, relu=True)  # fused add+relu via residual arg
+        # fused add+relu via residual arg; an SE block's tail is the SE op
+        self.bn2 = FusedBNAct(cout, relu=not se)
         self.downsample = downsample
+        if se:
+            self.se = SqueezeExcite(cout)
 
     def forward(self, x):
+        if "se" in self._modules:
+            # the shortcut first, as below; no junction deferral here
+            identity = x if self.downsample is None else self.downsample(x)
+            out = self.bn1(self.conv1(x))
+            return self.se(self.bn2(self.conv2(out)), identity)
         if self.downsample is not None:
             # downsample runs FIRST: python arg-evaluation order otherwise
             # clobbers conv2's BN-stats stash with the downsample conv's
@@ -138,7 +182,7 @@ class Bottleneck(nn.Module):
 
     def __init__(self, cin: int, cout: int, stride: int = 1,
                  downsample: Optional[nn.Module] = None, groups: int = 1,
-                 base_width: int = 64):
+                 base_width: int = 64, se: bool = False):
         super().__init__()
         # ResNeXt: the 3x3 conv is grouped and the inner width scales with
         # base_width; groups=1, base_width=64 is the plain bottleneck
@@ -148,10 +192,17 @@ class Bottleneck(nn.Module):
         self.conv2 = conv3x3(width, width, stride, groups)
         self.bn2 = FusedBNAct(width, relu=True)
         self.conv3 = conv1x1(width, cout * self.expansion)
-        self.bn3 = FusedBNAct(cout * self.expansion, relu=True)
+        self.bn3 = FusedBNAct(cout * self.expansion, relu=not se)
         self.downsample = downsample
+        if se:
+            self.se = SqueezeExcite(cout * self.expansion)
 
     def forward(self, x):
+        if "se" in self._modules:
+            identity = x if self.downsample is None else self.downsample(x)
+            out = self.bn1(self.conv1(x))
+            out = self.bn2(self.conv2(out))
+            return self.se(self.bn3(self.conv3(out)), identity)
         if self.downsample is not None:
             identity = self.downsample(x)   # first — see BasicBlock note
             out = self.bn1(self.conv1(x))
@@ -178,7 +229,8 @@ class Downsample(nn.Module):
 class ResNet(nn.Module):
     def __init__(self, block: Type[nn.Module], layers: List[int],
                  num_classes: int = 1000, small_input: bool = False,
-                 groups: int = 1, width_per_group: int = 64):
+                 groups: int = 1, width_per_group: int = 64,
+                 se: bool = False):
         super().__init__()
         if (groups, width_per_group) != (1, 64) and block is not Bottleneck:
             raise ValueError("groups / width_per_group need Bottleneck blocks")
@@ -186,6 +238,8 @@ class ResNet(nn.Module):
         # extra block arguments: none for the plain ResNets
         self._block_kw = ({} if (groups, width_per_group) == (1, 64) else
                           dict(groups=groups, base_width=width_per_group))
+        if se:
+            self._block_kw = dict(self._block_kw, se=True)
         self.cin = 64
         if small_input:  # CIFAR-style stem (BASELINE config 1)
             self.conv1 = FdaConv2d(3, 64, 3, stride=1, padding=1, bias=False)
@@ -277,6 +331,36 @@ def resnext101_64x4d(**kw):
     return ResNet(Bottleneck, [3, 4, 23, 3], groups=64, width_per_group=4, **kw)
 
 
+def se_resnet18(**kw):
+    return ResNet(BasicBlock, [2, 2, 2, 2], se=True, **kw)
+
+
+def se_resnet34(**kw):
+    return ResNet(BasicBlock, [3, 4, 6, 3], se=True, **kw)
+
+
+def se_resnet50(**kw):
+    return ResNet(Bottleneck, [3, 4, 6, 3], se=True, **kw)
+
+
+def se_resnet101(**kw):
+    return ResNet(Bottleneck, [3, 4, 23, 3], se=True, **kw)
+
+
+def se_resnet152(**kw):
+    return ResNet(Bottleneck, [3, 8, 36, 3], se=True, **kw)
+
+
+def se_resnext50_32x4d(**kw):
+    return ResNet(Bottleneck, [3, 4, 6, 3], groups=32, width_per_group=4,
+                  se=True, **kw)
+
+
+def se_resnext101_32x4d(**kw):
+    return ResNet(Bottleneck, [3, 4, 23, 3], groups=32, width_per_group=4,
+                  se=True, **kw)
+
+
 _ZOO = {
     "resnet18": resnet18,
     "resnet34": resnet34,
@@ -286,6 +370,13 @@ _ZOO = {
     "resnext50_32x4d": resnext50_32x4d,
     "resnext101_32x4d": resnext101_32x4d,
     "resnext101_64x4d": resnext101_64x4d,
+    "se_resnet18": se_resnet18,
+    "se_resnet34": se_resnet34,
+    "se_resnet50": se_resnet50,
+    "se_resnet101": se_resnet101,
+    "se_resnet152": se_resnet152,
+    "se_resnext50_32x4d": se_resnext50_32x4d,
+    "se_resnext101_32x4d": se_resnext101_32x4d,
 }
 
 

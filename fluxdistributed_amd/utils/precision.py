@@ -7,15 +7,16 @@ keep params fp32 for numerics), fp32 master weights in the fused optimizer.
 
 import torch
 
-from ..models.resnet import FusedBNAct
+from ..models.resnet import FusedBNAct, SqueezeExcite
 
 
 def to_mixed_bf16(model: torch.nn.Module) -> torch.nn.Module:
-    """Cast conv/linear params to bf16; keep norm-layer params + buffers fp32."""
+    """Cast conv/linear and squeeze-and-excitation params to bf16; keep
+    norm-layer params + buffers fp32."""
     for mod in model.modules():
         if isinstance(mod, FusedBNAct):
             continue
-        if isinstance(mod, (torch.nn.Conv2d, torch.nn.Linear)):
+        if isinstance(mod, (torch.nn.Conv2d, torch.nn.Linear, SqueezeExcite)):
             for name, p in list(mod._parameters.items()):
                 if p is not None:
                     mod._parameters[name] = torch.nn.Parameter(
