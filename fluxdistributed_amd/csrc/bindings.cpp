@@ -1248,6 +1248,131 @@ std::tuple<int64_t, int64_t, int64_t, int64_t> conv_grouped_config(
     return {p.th, p.tw, 1, p.ipb * px};
 }
 
+// ---- depthwise 3x3 conv (conv_dw.hip) --------------------------------------
+// Operands: channels_last bf16 activations and the bf16 weight [C,1,3,3],
+// whose bytes are [C][9] in contiguous and in channels_last form alike.
+// Checks in the order of the other conv entry points: dtype, layout, the
+// supported set, sizes, then the device.
+
+// The supported set: groups == C == K, C a multiple of 8, 3x3, padding 1,
+// stride 1 or 2.
+fda::ConvGeom dw_geometry(const char* op, int64_t N, int64_t C, int64_t H,
+                          int64_t W, int64_t sy, int64_t sx) {
+    TORCH_CHECK(C >= 8 && C % 8 == 0, op,
+                ": C must be a multiple of 8, got C=", C);
+    TORCH_CHECK(sy == sx && (sy == 1 || sy == 2), op,
+                ": stride must be (1,1) or (2,2), got ", sy, "x", sx);
+    TORCH_CHECK(N >= 1 && H >= 1 && W >= 1, op,
+                ": needs N, H, W >= 1, got N=", N, " H=", H, " W=", W);
+    TORCH_CHECK(N * H * W * C < (int64_t(1) << 40) && N <= INT32_MAX &&
+                    H <= INT32_MAX && W <= INT32_MAX && C <= INT32_MAX &&
+                    N * H * W <= INT32_MAX,
+                op, ": problem too large");
+    const int64_t P = (H - 1) / sy + 1, Q = (W - 1) / sx + 1;
+    return {(int)N, (int)H, (int)W, (int)C, (int)C, (int)P, (int)Q,
+            3, 3, (int)sy, (int)sx, 1, 1};
+}
+
+// w is the depthwise weight [C, 1, 3, 3] of C channels: dense bf16
+void check_dw_weight(const char* op, const at::Tensor& w, int64_t C) {
+    TORCH_CHECK(w.dim() == 4 && w.scalar_type() == at::kBFloat16 &&
+                    (w.is_contiguous() ||
+                     w.is_contiguous(at::MemoryFormat::ChannelsLast)),
+                op, ": w must be 4-D dense bf16");
+    TORCH_CHECK(w.size(0) == C && w.size(1) == 1 && w.size(2) == 3 &&
+                    w.size(3) == 3,
+                op, ": w is [", w.size(0), ", ", w.size(1), ", ", w.size(2),
+                ", ", w.size(3), "] but a depthwise 3x3 conv of ", C,
+                " channels needs [", C, ", 1, 3, 3]");
+    check_aligned16(op, "w", w);
+}
+
+at::Tensor conv_dw_fwd(at::Tensor x, at::Tensor w, int64_t sy, int64_t sx) {
+    const char* op = "conv_dw_fwd";
+    check_cl_bf16(op, "x", x);
+    check_aligned16(op, "x", x);
+    const auto g = dw_geometry(op, x.size(0), x.size(1), x.size(2),
+                               x.size(3), sy, sx);
+    check_dw_weight(op, w, g.C);
+    check_device(op, {x, w});
+    auto y = at::empty({g.N, g.C, g.P, g.Q},
+                       x.options().memory_format(at::MemoryFormat::ChannelsLast));
+    fda::conv_dw_launch(x.data_ptr(), w.data_ptr(), y.data_ptr(), g,
+                        fda::CONV_FWD, cur_stream());
+    return y;
+}
+
+// dy [N,C,P,Q], w [C,1,3,3] -> dx [N,C,H,W], every element written
+at::Tensor conv_dw_dgrad(at::Tensor dy, at::Tensor w, int64_t H, int64_t W,
+                         int64_t sy, int64_t sx) {
+    const char* op = "conv_dw_dgrad";
+    check_cl_bf16(op, "dy", dy);
+    check_aligned16(op, "dy", dy);
+    const auto g = dw_geometry(op, dy.size(0), dy.size(1), H, W, sy, sx);
+    check_dw_weight(op, w, g.C);
+    check_dy(op, dy, g);
+    check_device(op, {dy, w});
+    auto dx = at::empty({g.N, g.C, g.H, g.W},
+                        dy.options().memory_format(at::MemoryFormat::ChannelsLast));
+    fda::conv_dw_launch(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), g,
+                        fda::CONV_DGRAD, cur_stream());
+    return dx;
+}
+
+// dy [N,C,P,Q], x [N,C,H,W] -> ws [C][9] fp32: the weight's memory order.
+// More than one chunk: per-chunk slabs and the ordered fold.
+at::Tensor conv_dw_wgrad(at::Tensor dy, at::Tensor x, int64_t sy,
+                         int64_t sx) {
+    const char* op = "conv_dw_wgrad";
+    check_cl_bf16(op, "dy", dy);
+    check_cl_bf16(op, "x", x);
+    check_aligned16(op, "dy", dy);
+    check_aligned16(op, "x", x);
+    const auto g = dw_geometry(op, x.size(0), x.size(1), x.size(2),
+                               x.size(3), sy, sx);
+    TORCH_CHECK(dy.size(0) == x.size(0) && dy.size(1) == x.size(1), op,
+                ": dy is [", dy.size(0), ", ", dy.size(1), ", ..] but x is [",
+                x.size(0), ", ", x.size(1), ", ..]");
+    check_dy(op, dy, g);
+    const auto p = fda::conv_dw_plan(g.N, g.H, g.W, g.C, g.sy,
+                                     fda::CONV_DW_WGRAD);
+    const int64_t n = (int64_t)g.C * 9;
+    check_device(op, {dy, x});
+    const auto f32 = x.options().dtype(at::kFloat).memory_format(
+        at::MemoryFormat::Contiguous);
+    auto ws = at::empty({g.C, 9}, f32);
+    if (p.nch == 1) {
+        fda::conv_dw_wgrad_launch(dy.data_ptr(), x.data_ptr(),
+                                  ws.data_ptr<float>(), g, cur_stream());
+        return ws;
+    }
+    auto slab = at::empty({p.nch * n}, f32);
+    fda::conv_dw_wgrad_launch(dy.data_ptr(), x.data_ptr(),
+                              slab.data_ptr<float>(), g, cur_stream());
+    fda::wgrad_slab_fold_launch(slab.data_ptr<float>(), p.nch, n,
+                                ws.data_ptr(), false, cur_stream());
+    return ws;
+}
+
+// What the depthwise kernels run for x [N,C,H,W]: (th, tw, nch, units per
+// chunk). fwd / dgrad: a unit is a strip of tw output columns walked th rows
+// down by one pixel group (for a stride-2 dgrad: of a parity class); one
+// "chunk", the units a block takes = its pixel groups. wgrad: a unit is one
+// (image, output row), th = 1 and tw = Q, nch chunks of that many units.
+std::tuple<int64_t, int64_t, int64_t, int64_t> conv_dw_config(
+    int64_t N, int64_t H, int64_t W, int64_t C, int64_t stride,
+    const std::string& mode) {
+    const char* op = "conv_dw_config";
+    const auto g = dw_geometry(op, N, C, H, W, stride, stride);
+    TORCH_CHECK(mode == "fwd" || mode == "dgrad" || mode == "wgrad", op,
+                ": mode must be fwd, dgrad or wgrad");
+    const int m = mode == "fwd" ? fda::CONV_DW_FWD
+                  : mode == "dgrad" ? fda::CONV_DW_DGRAD
+                                    : fda::CONV_DW_WGRAD;
+    const auto p = fda::conv_dw_plan(g.N, g.H, g.W, g.C, g.sy, m);
+    return {p.th, p.tw, p.nch, p.upc};
+}
+
 // ---- squeeze-and-excitation (se.hip) ---------------------------------------
 // u, identity, out, gout: channels_last bf16 [N,C,H,W]. w1 [Cr,C], b1 [Cr],
 // w2 [C,Cr], b2 [C]: contiguous bf16. s, z [N,C] and h [N,Cr]: fp32.
@@ -1881,6 +2006,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("conv_grouped_config", &conv_grouped_config,
           "(th, tw, nch, pixels per chunk) the grouped conv kernels run; "
           "mode fwd/dgrad/wgrad");
+    m.def("conv_dw_fwd", &conv_dw_fwd,
+          "depthwise 3x3 conv forward (NHWC bf16, C % 8 == 0, stride 1|2, "
+          "weight [C,1,3,3] as stored)");
+    m.def("conv_dw_dgrad", &conv_dw_dgrad,
+          "depthwise 3x3 conv input-grad, every dx element written once");
+    m.def("conv_dw_wgrad", &conv_dw_wgrad,
+          "depthwise 3x3 conv weight-grad [C][9] fp32: per-chunk slabs + "
+          "ordered fold, bit-reproducible");
+    m.def("conv_dw_config", &conv_dw_config,
+          "(th, tw, nch, units per chunk) the depthwise conv kernels run; "
+          "mode fwd | dgrad | wgrad");
     m.def("se_fwd", &se_fwd,
           "squeeze-and-excitation tail: (out, s, h, z) = relu(u * s + "
           "identity) with the fp32 gate and its saved intermediates");

@@ -348,6 +348,33 @@ void conv_grouped_launch(const void* src, const void* w, void* out,
 void conv_grouped_wgrad_launch(const void* dy, const void* x, float* ws,
                                const ConvGeom& g, int cpg, hipStream_t stream);
 
+// Depthwise 3x3 conv, NHWC bf16 (conv_dw.hip): groups == C == K, C % 8 == 0,
+// padding 1, stride 1 or 2. The geometry is a ConvGeom with K == C,
+// R == S == 3; the weight is always w [C][9] as stored ([C,1,3,3]).
+// What a launch runs: a lane owns 8 channels; the C/8 channel lanes go in
+// nslab slabs of lps lanes through the grid, and a block of 256 lanes has
+// `groups` = 256 / lps pixel groups. fwd / dgrad: a pixel group walks th
+// output rows of a strip of tw columns (for a stride-2 dgrad per parity
+// class). wgrad: a unit is one (image, output row) of tw = Q pixels, nch
+// chunks of upc units each. blocks: the grid.
+constexpr int CONV_DW_FWD = 0;
+constexpr int CONV_DW_DGRAD = 1;
+constexpr int CONV_DW_WGRAD = 2;
+struct ConvDwPlan {
+    int th, tw, lps, nslab, groups, classes, nch, upc;
+    long blocks;
+};
+ConvDwPlan conv_dw_plan(int N, int H, int W, int C, int stride, int mode);
+// fwd:   src=x [N,H,W,C],  out=y [N,P,Q,C]
+// dgrad: src=dy [N,P,Q,C], out=dx [N,H,W,C], every element written
+void conv_dw_launch(const void* src, const void* w, void* out,
+                    const ConvGeom& g, ConvMode mode, hipStream_t stream);
+// plan.nch == 1: ws is the result [C][9] fp32. nch > 1: ws is [nch][C][9],
+// chunk c stores into slab c and wgrad_slab_fold_launch sums them. Every
+// element is written exactly once either way.
+void conv_dw_wgrad_launch(const void* dy, const void* x, float* ws,
+                          const ConvGeom& g, hipStream_t stream);
+
 // Squeeze-and-Excitation block tail (se.hip), NHWC bf16 activations:
 //   out = relu(u * s[n][c] + identity), s = sigmoid(W2 relu(W1 mean_hw(u) +
 //   b1) + b2). C % 64 == 0, 64 <= C <= 2048; Cr % 4 == 0, 4 <= Cr <= 128.

@@ -1,0 +1,103 @@
+"""MobileNetV1 (Howard et al. 2017, "MobileNets: Efficient Convolutional
+Neural Networks for Mobile Vision Applications"), written from scratch for
+this framework from the paper's layer table.
+
+A 3x3 stride-2 stem, 13 depthwise-separable blocks of [depthwise 3x3, BN,
+ReLU, pointwise 1x1, BN, ReLU], global average pool and one dense layer.
+On the GPU the depthwise convs run on csrc/conv_dw.hip (FLUXDIST_CONV_DW),
+the pointwise convs on conv_igemm, BN+ReLU is the fused op. At width 1.0 the
+stem (K = 32) and the first pointwise conv (C = 32) are outside every native
+conv path and stay on the library; so do the two 32-channel BNs (after the
+stem and after the first depthwise conv), because the fused BN kernels train
+multiples of 64 channels only (BNAct below).
+
+Conv weights are bias-free, like the ResNets'.
+"""
+
+from typing import List, Tuple
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from ..ops.conv import FdaConv2d
+from ..ops.functional import GlobalAvgPool
+from ..ops.linear import FdaLinear
+from .resnet import _ZOO, FusedBNAct, ResNet
+
+# (output channels, stride) of the 13 depthwise-separable blocks
+_BLOCKS: List[Tuple[int, int]] = (
+    [(64, 1), (128, 2), (128, 1), (256, 2), (256, 1), (512, 2)]
+    + [(512, 1)] * 5 + [(1024, 2), (1024, 1)])
+
+
+def _width(channels: int, mult: float) -> int:
+    """channels * mult rounded to a multiple of 8, at least 8."""
+    return max(8, int(channels * mult + 4) // 8 * 8)
+
+
+class BNAct(FusedBNAct):
+    """FusedBNAct for any channel count. The native BN kernels train
+    C % 64 == 0 only; a narrower layer on the GPU (32 channels at width 1.0,
+    other widths at other multipliers) is the composition of library ops
+    that batch_norm_act uses as its CPU form, in fp32. Same parameters,
+    buffers and state dict either way."""
+
+    def forward(self, x):
+        if self.num_features % 64 == 0 or not x.is_cuda:
+            return super().forward(x)
+        if self.training:
+            self._nbt_pending += 1
+        out = F.batch_norm(x.float(), self.running_mean, self.running_var,
+                           self.weight, self.bias, self.training,
+                           self.momentum, self.eps)
+        return (torch.relu(out) if self.relu else out).to(x.dtype)
+
+
+class DepthwiseSeparable(nn.Module):
+    """depthwise 3x3 (stride) -> BN -> ReLU -> pointwise 1x1 -> BN -> ReLU"""
+
+    def __init__(self, cin: int, cout: int, stride: int):
+        super().__init__()
+        self.dw = FdaConv2d(cin, cin, 3, stride=stride, padding=1, groups=cin,
+                            bias=False)
+        self.bn1 = BNAct(cin, relu=True)
+        self.pw = FdaConv2d(cin, cout, 1, bias=False)
+        self.bn2 = BNAct(cout, relu=True)
+
+    def forward(self, x):
+        x = self.bn1(self.dw(x))
+        return self.bn2(self.pw(x))
+
+
+class MobileNetV1(nn.Module):
+    def __init__(self, num_classes: int = 1000, small_input: bool = False,
+                 width_mult: float = 1.0):
+        super().__init__()
+        self.small_input = small_input
+        cin = _width(32, width_mult)
+        # small_input: a stride-1 stem, as the ResNets' CIFAR stem
+        self.conv1 = FdaConv2d(3, cin, 3, stride=1 if small_input else 2,
+                               padding=1, bias=False)
+        self.bn1 = BNAct(cin, relu=True)
+        blocks = []
+        for cout, stride in _BLOCKS:
+            cout = _width(cout, width_mult)
+            blocks.append(DepthwiseSeparable(cin, cout, stride))
+            cin = cout
+        self.features = nn.Sequential(*blocks)
+        self.avgpool = GlobalAvgPool()
+        self.fc = FdaLinear(cin, num_classes)
+        ResNet._init_weights(self)
+
+    def forward(self, x):
+        x = self.bn1(self.conv1(x))
+        x = self.features(x)
+        return self.fc(self.avgpool(x))
+
+
+def mobilenet_v1(**kw):
+    return MobileNetV1(**kw)
+
+
+_ZOO["mobilenet_v1"] = mobilenet_v1

@@ -380,7 +380,8 @@ _ZOO = {
 }
 
 
-def build_model(name: str, num_classes: int = 1000, small_input: bool = False) -> ResNet:
+def build_model(name: str, num_classes: int = 1000,
+                small_input: bool = False) -> nn.Module:
     if name not in _ZOO:
         raise ValueError(f"unknown model '{name}'; choose from {sorted(_ZOO)}")
     return _ZOO[name](num_classes=num_classes, small_input=small_input)

@@ -8,6 +8,7 @@ with effective TFLOP/s. Run on a GPU box:
     python tools/bench_conv.py --mode wgrad --iters 200   # wgrad arms only
     python tools/bench_conv.py --dtype fp32   # conv_f32 kernels vs aten fp32
     python tools/bench_conv.py --groups       # conv_grouped vs the library
+    python tools/bench_conv.py --depthwise    # conv_dw vs the library
 """
 
 import argparse
@@ -283,6 +284,80 @@ def grouped_arms(args):
           f"| {tot[2]:8.1f} {tot[3]:8.1f} | {tot[4]:8.1f} {tot[5]:8.1f}")
 
 
+# depthwise 3x3 convs of MobileNetV1: (C, input H = W, stride, count)
+DW_SHAPES = [
+    (32, 112, 1, 1),
+    (64, 112, 2, 1),
+    (128, 56, 1, 1),
+    (128, 56, 2, 1),
+    (256, 28, 1, 1),
+    (256, 28, 2, 1),
+    (512, 14, 1, 5),
+    (512, 14, 2, 1),
+    (1024, 7, 1, 1),
+]
+
+
+def depthwise_arms(args):
+    """Depthwise 3x3: the conv_dw kernels against the library's depthwise
+    conv on the same tensors, per shape and per leg; figures as for --groups.
+    min MB: the leg's compulsory traffic (fwd and dgrad: the input once and
+    the output once; wgrad: x and dy once; the same bytes for all three), and
+    after it the rate each native leg reaches on those bytes, in TB/s."""
+    C_ = require_native("conv_dw_fwd")
+    torch.backends.cudnn.benchmark = True
+    n = args.batch
+    print(f"# batch={n} depthwise bf16, us per call: median of {args.repeats} "
+          f"blocks of {args.iters} calls")
+    print(f"{'shape':22s} {'fda_fwd':>8s} {'lib_fwd':>8s} | {'fda_dg':>8s} "
+          f"{'lib_dg':>8s} | {'fda_wg':>8s} {'lib_wg':>8s} | {'min MB':>7s}  "
+          f"fwd/dg/wg TB/s  wgrad (nch, rows)")
+    shapes = DW_SHAPES if args.only < 0 else [DW_SHAPES[args.only]]
+    tot = [0.0] * 6
+    cl = torch.channels_last
+    for (c, h, s, cnt) in shapes:
+        P = (h - 1) // s + 1
+        x = torch.randn(n, c, h, h, device="cuda").bfloat16() \
+            .contiguous(memory_format=cl)
+        wt = torch.randn(c, 1, 3, 3, device="cuda").bfloat16()
+        gy = torch.randn(n, c, P, P, device="cuda").bfloat16() \
+            .contiguous(memory_format=cl)
+
+        def lib_bwd(mask):
+            return torch.ops.aten.convolution_backward(
+                gy, x, wt, None, [s, s], [1, 1], [1, 1], False, [0, 0], c,
+                mask)
+        arms = [
+            lambda: C_.conv_dw_fwd(x, wt, s, s),
+            lambda: torch.nn.functional.conv2d(x, wt, None, s, 1, 1, c),
+            lambda: C_.conv_dw_dgrad(gy, wt, h, h, s, s),
+            lambda: lib_bwd([True, False, False]),
+            lambda: C_.conv_dw_wgrad(gy, x, s, s),
+            lambda: lib_bwd([False, True, False]),
+        ]
+        ts = [[] for _ in arms]
+        for _ in range(args.repeats):
+            for i, fn in enumerate(arms):
+                if args.fda_only and i % 2:
+                    ts[i].append(float("inf"))
+                else:
+                    ts[i].append(event_us(fn, args.iters))
+        med = [sorted(t)[len(t) // 2] for t in ts]
+        for i in range(6):
+            tot[i] += med[i] * cnt
+        nbytes = 2.0 * (x.numel() + gy.numel())
+        rate = [nbytes / med[i] / 1e6 for i in (0, 2, 4)]   # B/us -> TB/s
+        cf = C_.conv_dw_config(n, h, h, c, s, "wgrad")
+        name = f"{c}x{h}x{h} s{s} x{cnt}"
+        print(f"{name:22s} {med[0]:8.1f} {med[1]:8.1f} | {med[2]:8.1f} "
+              f"{med[3]:8.1f} | {med[4]:8.1f} {med[5]:8.1f} | "
+              f"{nbytes / 1e6:7.1f}  "
+              f"{rate[0]:.2f}/{rate[1]:.2f}/{rate[2]:.2f}"
+              f"  ({cf[2]}, {cf[3]})", flush=True)
+    print(f"{'TOTAL (weighted by count)':22s} {tot[0]:8.1f} {tot[1]:8.1f} "
+          f"| {tot[2]:8.1f} {tot[3]:8.1f} | {tot[4]:8.1f} {tot[5]:8.1f}")
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, default=96)
@@ -305,8 +380,14 @@ def main():
                    help="the grouped 3x3 shapes of ResNeXt-50 32x4d: the "
                         "conv_grouped kernels against the library, all three "
                         "legs")
+    p.add_argument("--depthwise", action="store_true",
+                   help="the depthwise 3x3 shapes of MobileNetV1: the conv_dw "
+                        "kernels against the library, all three legs, with "
+                        "the rate reached on the compulsory bytes")
     args = p.parse_args()
     assert torch.cuda.is_available()
+    if args.depthwise:
+        return depthwise_arms(args)
     if args.groups:
         return grouped_arms(args)
     if args.dtype == "fp32":
