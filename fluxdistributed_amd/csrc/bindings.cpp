@@ -1373,6 +1373,141 @@ std::tuple<int64_t, int64_t, int64_t, int64_t> conv_dw_config(
     return {p.th, p.tw, p.nch, p.upc};
 }
 
+// ---- narrow pointwise conv (conv_pw.hip) ------------------------------------
+// Operands: channels_last bf16 activations and the bf16 weight [K,C,1,1],
+// whose bytes are [K][C] in contiguous and in channels_last form alike.
+// Checks in the order of the other conv entry points: dtype, layout, the
+// supported set, sizes, then the device.
+
+void check_pw_channels(const char* op, int64_t C, int64_t K) {
+    TORCH_CHECK(C % 8 == 0 && C >= 8 && C <= 256 && K % 8 == 0 && K >= 8 &&
+                    K <= 256,
+                op, ": C and K must be multiples of 8 in [8, 256], got C=", C,
+                " K=", K);
+}
+
+// w is a pointwise weight [K, C, 1, 1]: dense bf16
+void check_pw_weight(const char* op, const at::Tensor& w) {
+    TORCH_CHECK(w.dim() == 4 && w.scalar_type() == at::kBFloat16 &&
+                    (w.is_contiguous() ||
+                     w.is_contiguous(at::MemoryFormat::ChannelsLast)),
+                op, ": w must be 4-D dense bf16");
+    TORCH_CHECK(w.size(2) == 1 && w.size(3) == 1, op, ": w is [", w.size(0),
+                ", ", w.size(1), ", ", w.size(2), ", ", w.size(3),
+                "] but a pointwise conv needs [K, C, 1, 1]");
+    check_aligned16(op, "w", w);
+}
+
+// pixels of a channels_last activation, M = N*H*W <= INT32_MAX
+int64_t pw_pixels(const char* op, const at::Tensor& t) {
+    TORCH_CHECK(t.size(0) >= 1 && t.size(2) >= 1 && t.size(3) >= 1, op,
+                ": needs N, H, W >= 1, got N=", t.size(0), " H=", t.size(2),
+                " W=", t.size(3));
+    TORCH_CHECK(t.size(0) <= INT32_MAX && t.size(2) <= INT32_MAX &&
+                    t.size(3) <= INT32_MAX &&
+                    t.size(0) * t.size(2) <= INT32_MAX &&
+                    t.size(0) * t.size(2) * t.size(3) <= INT32_MAX,
+                op, ": problem too large (N*H*W must fit int32)");
+    return t.size(0) * t.size(2) * t.size(3);
+}
+
+// src [N,Cs,H,W] against w [K,C,1,1] -> [N,Co,H,W]: forward (Cs = C, Co = K)
+// or dgrad (Cs = K, Co = C, every element written)
+at::Tensor conv_pw_apply(const char* op, const char* name,
+                         const at::Tensor& src, const at::Tensor& w,
+                         int mode) {
+    check_cl_bf16(op, name, src);
+    check_aligned16(op, name, src);
+    check_pw_weight(op, w);
+    const int64_t K = w.size(0), C = w.size(1);
+    check_pw_channels(op, C, K);
+    const bool fwd = mode == fda::CONV_PW_FWD;
+    TORCH_CHECK(src.size(1) == (fwd ? C : K), op, ": ", name, " has ",
+                src.size(1), " channels but w is [", K, ", ", C, ", 1, 1]");
+    const int64_t M = pw_pixels(op, src);
+    check_device(op, {src, w});
+    auto out = at::empty(
+        {src.size(0), fwd ? K : C, src.size(2), src.size(3)},
+        src.options().memory_format(at::MemoryFormat::ChannelsLast));
+    fda::conv_pw_launch(src.data_ptr(), w.data_ptr(), out.data_ptr(), M,
+                        (int)C, (int)K, mode, cur_stream());
+    return out;
+}
+
+at::Tensor conv_pw_fwd(at::Tensor x, at::Tensor w) {
+    return conv_pw_apply("conv_pw_fwd", "x", x, w, fda::CONV_PW_FWD);
+}
+
+at::Tensor conv_pw_dgrad(at::Tensor dy, at::Tensor w) {
+    return conv_pw_apply("conv_pw_dgrad", "dy", dy, w, fda::CONV_PW_DGRAD);
+}
+
+// dy [N,K,H,W], x [N,C,H,W] -> ws [K][C] fp32: the weight's memory order.
+// More than one chunk: per-chunk slabs and the ordered fold.
+at::Tensor conv_pw_wgrad(at::Tensor dy, at::Tensor x) {
+    const char* op = "conv_pw_wgrad";
+    check_cl_bf16(op, "dy", dy);
+    check_cl_bf16(op, "x", x);
+    check_aligned16(op, "dy", dy);
+    check_aligned16(op, "x", x);
+    const int64_t K = dy.size(1), C = x.size(1);
+    check_pw_channels(op, C, K);
+    TORCH_CHECK(dy.size(0) == x.size(0) && dy.size(2) == x.size(2) &&
+                    dy.size(3) == x.size(3),
+                op, ": dy is [", dy.size(0), ", .., ", dy.size(2), ", ",
+                dy.size(3), "] but x is [", x.size(0), ", .., ", x.size(2),
+                ", ", x.size(3), "]");
+    const int64_t M = pw_pixels(op, x);
+    const auto p = fda::conv_pw_plan(M, (int)C, (int)K, fda::CONV_PW_WGRAD);
+    const int64_t n = K * C;
+    check_device(op, {dy, x});
+    const auto f32 = x.options().dtype(at::kFloat).memory_format(
+        at::MemoryFormat::Contiguous);
+    auto ws = at::empty({K, C}, f32);
+    if (p.nch == 1) {
+        fda::conv_pw_wgrad_launch(dy.data_ptr(), x.data_ptr(),
+                                  ws.data_ptr<float>(), M, (int)C, (int)K,
+                                  cur_stream());
+        return ws;
+    }
+    auto slab = at::empty({p.nch * n}, f32);
+    fda::conv_pw_wgrad_launch(dy.data_ptr(), x.data_ptr(),
+                              slab.data_ptr<float>(), M, (int)C, (int)K,
+                              cur_stream());
+    if (p.fold_g == 1) {
+        fda::wgrad_slab_fold_launch(slab.data_ptr<float>(), p.nch, n,
+                                    ws.data_ptr(), false, cur_stream());
+        return ws;
+    }
+    // two levels: sums over j of slab[j*g + i], then over i, each in order
+    auto part = at::empty({p.fold_g * n}, f32);
+    fda::wgrad_slab_fold_launch(slab.data_ptr<float>(), p.nch / p.fold_g,
+                                p.fold_g * n, part.data_ptr(), false,
+                                cur_stream());
+    fda::wgrad_slab_fold_launch(part.data_ptr<float>(), p.fold_g, n,
+                                ws.data_ptr(), false, cur_stream());
+    return ws;
+}
+
+// What the pointwise kernels run for M pixels. fwd / dgrad: (output slabs =
+// waves per pixel tile, pixel groups per block, grid blocks, tiles per wave).
+// wgrad: (k-slabs, c-slabs, nch, pixels per chunk).
+std::tuple<int64_t, int64_t, int64_t, int64_t> conv_pw_config(
+    int64_t M, int64_t C, int64_t K, const std::string& mode) {
+    const char* op = "conv_pw_config";
+    check_pw_channels(op, C, K);
+    TORCH_CHECK(M >= 1 && M <= INT32_MAX, op,
+                ": M must be in [1, INT32_MAX], got ", M);
+    TORCH_CHECK(mode == "fwd" || mode == "dgrad" || mode == "wgrad", op,
+                ": mode must be fwd, dgrad or wgrad");
+    const int m = mode == "fwd" ? fda::CONV_PW_FWD
+                  : mode == "dgrad" ? fda::CONV_PW_DGRAD
+                                    : fda::CONV_PW_WGRAD;
+    const auto p = fda::conv_pw_plan(M, (int)C, (int)K, m);
+    if (m == fda::CONV_PW_WGRAD) return {p.kslabs, p.cslabs, p.nch, p.mch};
+    return {p.nslab, p.pgs, p.gx, p.tpw};
+}
+
 // ---- squeeze-and-excitation (se.hip) ---------------------------------------
 // u, identity, out, gout: channels_last bf16 [N,C,H,W]. w1 [Cr,C], b1 [Cr],
 // w2 [C,Cr], b2 [C]: contiguous bf16. s, z [N,C] and h [N,Cr]: fp32.
@@ -2017,6 +2152,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("conv_dw_config", &conv_dw_config,
           "(th, tw, nch, units per chunk) the depthwise conv kernels run; "
           "mode fwd | dgrad | wgrad");
+    m.def("conv_pw_fwd", &conv_pw_fwd,
+          "narrow pointwise conv forward (NHWC bf16, C, K % 8 == 0 in "
+          "[8, 256], weight [K,C,1,1] as stored, kept in registers)");
+    m.def("conv_pw_dgrad", &conv_pw_dgrad,
+          "narrow pointwise conv input-grad from the weight as stored");
+    m.def("conv_pw_wgrad", &conv_pw_wgrad,
+          "narrow pointwise conv weight-grad [K][C] fp32: per-chunk slabs + "
+          "ordered fold, bit-reproducible");
+    m.def("conv_pw_config", &conv_pw_config,
+          "what the pointwise kernels run for M pixels; mode fwd | dgrad | "
+          "wgrad (wgrad: elements 2, 3 are nch and pixels per chunk)");
     m.def("se_fwd", &se_fwd,
           "squeeze-and-excitation tail: (out, s, h, z) = relu(u * s + "
           "identity) with the fp32 gate and its saved intermediates");

@@ -375,6 +375,36 @@ void conv_dw_launch(const void* src, const void* w, void* out,
 void conv_dw_wgrad_launch(const void* dy, const void* x, float* ws,
                           const ConvGeom& g, hipStream_t stream);
 
+// Narrow pointwise (1x1) conv, NHWC bf16 (conv_pw.hip): stride 1, padding 0,
+// groups 1, C and K multiples of 8 in [8, 256]. With M = N*H*W pixels it is a
+// skinny GEMM over M rows; the weight is always w [K][C] as stored.
+// What a launch runs. fwd / dgrad: the outputs go in nslab slabs of at most
+// 64 channels, one per wave; a block has nslab * pgs waves, its pgs pixel
+// groups walk 16-pixel tiles, tpw tiles per wave by the grid of gx blocks.
+// wgrad: a block owns a 64 x 64 (k-slab, c-slab) pair of dw and one of nch
+// chunks of mch pixels (whole 128-pixel staging rounds); blocks: the grid.
+constexpr int CONV_PW_FWD = 0;
+constexpr int CONV_PW_DGRAD = 1;
+constexpr int CONV_PW_WGRAD = 2;
+struct ConvPwPlan {
+    int nslab, pgs, tpw, gx;   // fwd / dgrad
+    int kslabs, cslabs, nch, mch;   // wgrad
+    int fold_g;   // wgrad: 1, or the group count of a two-level fold
+    long blocks;
+};
+ConvPwPlan conv_pw_plan(long M, int C, int K, int mode);
+// fwd:   src=x [M][C],  out=y [M][K]
+// dgrad: src=dy [M][K], out=dx [M][C], every element written
+void conv_pw_launch(const void* src, const void* w, void* out, long M, int C,
+                    int K, int mode, hipStream_t stream);
+// plan.nch == 1: ws is the result [K][C] fp32. nch > 1: ws is [nch][K][C],
+// chunk c stores into slab c and wgrad_slab_fold_launch sums them: at once
+// (fold_g == 1), or first the nch / fold_g slabs j*fold_g + i of every i,
+// the slabs read as [nch / fold_g][fold_g*K*C], then the fold_g sums. Every
+// element is written exactly once either way.
+void conv_pw_wgrad_launch(const void* dy, const void* x, float* ws, long M,
+                          int C, int K, hipStream_t stream);
+
 // Squeeze-and-Excitation block tail (se.hip), NHWC bf16 activations:
 //   out = relu(u * s[n][c] + identity), s = sigmoid(W2 relu(W1 mean_hw(u) +
 //   b1) + b2). C % 64 == 0, 64 <= C <= 2048; Cr % 4 == 0, 4 <= Cr <= 128.

@@ -5,11 +5,13 @@ this framework from the paper's layer table.
 A 3x3 stride-2 stem, 13 depthwise-separable blocks of [depthwise 3x3, BN,
 ReLU, pointwise 1x1, BN, ReLU], global average pool and one dense layer.
 On the GPU the depthwise convs run on csrc/conv_dw.hip (FLUXDIST_CONV_DW),
-the pointwise convs on conv_igemm, BN+ReLU is the fused op. At width 1.0 the
-stem (K = 32) and the first pointwise conv (C = 32) are outside every native
-conv path and stay on the library; so do the two 32-channel BNs (after the
-stem and after the first depthwise conv), because the fused BN kernels train
-multiples of 64 channels only (BNAct below).
+the pointwise convs on conv_igemm where both channel counts are multiples of
+64 and, with FLUXDIST_CONV_PW=1, on csrc/conv_pw.hip where they are narrower
+(the first one at width 1.0, most of them at smaller widths, up to 256
+channels); BN+ReLU is the fused op. At width 1.0 the stem (K = 32) is outside
+every native conv path and stays on the library; so do the two 32-channel BNs
+(after the stem and after the first depthwise conv), because the fused BN
+kernels train multiples of 64 channels only (BNAct below).
 
 Conv weights are bias-free, like the ResNets'.
 """

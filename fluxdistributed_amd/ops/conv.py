@@ -27,6 +27,18 @@ autograd. On by default (FLUXDIST_CONV_DW=1): against the library's depthwise
 conv it is faster on every MobileNetV1 shape and leg and the MobileNetV1 step
 is 2.21x faster (profiles/conv_dw.md).
 
+Narrow pointwise convs (1x1, stride 1, padding 0, groups 1, C and K multiples
+of 8 in [8, 256]: the pointwise halves of depthwise-separable blocks) have
+csrc/conv_pw.hip: bf16, the weight [K][C] read as stored and held in
+registers by all of forward and dgrad, the activation read once, wgrad through
+per-chunk slabs and the ordered fold. Plain autograd. It sits behind
+conv_igemm, so shapes with both channel counts multiples of 64 stay there. The
+path is opt-in (FLUXDIST_CONV_PW=1): against the library it is faster in 13 of
+15 measured shape-legs of MobileNetV1 but slower in the forward (43 vs 36 us)
+and the wgrad (48 vs 47 us) of 32 -> 64 at 112x112, and the MobileNetV1 step
+does not move beyond the spread (profiles/conv_pw.md), so by the rule that
+defaults are measured winners the default is 0.
+
 fp32 operands have a native path of their own, csrc/conv_f32.hip on the
 fp32 MFMA (v_mfma_f32_16x16x4_f32): the same constraints (NHWC, dilation 1,
 groups 1, C and K multiples of 64), forward, dgrad from the untransposed
@@ -39,8 +51,8 @@ so by the rule that defaults are measured winners the default is 0.
 
 Env:
   FLUXDIST_CONV=miopen   force the library path everywhere (A/B testing)
-  FLUXDIST_CONV=fda      force the native path (errors on shapes neither
-                         native path supports)
+  FLUXDIST_CONV=fda      force the native path (errors on shapes no native
+                         path supports)
   FLUXDIST_CONV_F32=1|0  fp32 body convs on conv_f32.hip (1) or the library
                          (0, the default). Read at call time. FLUXDIST_CONV=fda
                          implies 1.
@@ -50,6 +62,10 @@ Env:
                          implies 1.
   FLUXDIST_CONV_DW=1|0   depthwise 3x3 convs on conv_dw.hip (1, the default)
                          or the library (0). Read at call time.
+                         FLUXDIST_CONV=miopen overrides it, FLUXDIST_CONV=fda
+                         implies 1.
+  FLUXDIST_CONV_PW=1|0   narrow pointwise convs on conv_pw.hip (1) or the
+                         library (0, the default). Read at call time.
                          FLUXDIST_CONV=miopen overrides it, FLUXDIST_CONV=fda
                          implies 1.
   FLUXDIST_WGRAD_SLAB=0  weight-grads into flat G: atomic workspace + queued
@@ -151,6 +167,28 @@ def _native_dw_supported(x: torch.Tensor, w: torch.Tensor, stride, padding,
         return False
     C = x.shape[1]
     if groups != C or tuple(w.shape) != (C, 1, 3, 3) or C % 8 != 0:
+        return False
+    return load_native() is not None
+
+
+_CONV_PW_DEFAULT = "0"
+
+
+def _native_pw_supported(x: torch.Tensor, w: torch.Tensor, stride, padding,
+                         dilation, groups) -> bool:
+    """Pointwise convs the conv_pw kernels serve, FLUXDIST_CONV_PW aside:
+    bf16, 1x1, stride 1, padding 0, groups 1, C and K multiples of 8 in
+    [8, 256]."""
+    if os.environ.get("FLUXDIST_CONV", "") == "miopen":
+        return False
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16):
+        return False
+    if groups != 1 or _pair(dilation) != (1, 1) or _pair(padding) != (0, 0):
+        return False
+    if _pair(stride) != (1, 1) or tuple(w.shape[2:]) != (1, 1):
+        return False
+    C, K = x.shape[1], w.shape[0]
+    if C % 8 != 0 or K % 8 != 0 or not (8 <= C <= 256 and 8 <= K <= 256):
         return False
     return load_native() is not None
 
@@ -357,6 +395,37 @@ class _FdaConv2dDepthwise(torch.autograd.Function):
         return dx, dw, None
 
 
+class _FdaConv2dPointwise(torch.autograd.Function):
+    """Narrow 1x1 forward, input-grad and weight-grad on the conv_pw kernels.
+    All three read the weight as stored ([K,C,1,1]: [K][C] in memory,
+    contiguous or channels_last); the weight-grad comes back fp32 in that
+    memory order and is cast once. Plain autograd: no conv->BN stats, no
+    arenas, no direct write into flat G."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        C = require_native("conv_pw_fwd")
+        clear_conv_stats()
+        xc = x.contiguous(memory_format=torch.channels_last)
+        wc = weight.contiguous(memory_format=torch.channels_last)
+        y = C.conv_pw_fwd(xc, wc)
+        ctx.save_for_backward(xc, wc)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        C = require_native("conv_pw_dgrad")
+        gy = gy.contiguous(memory_format=torch.channels_last)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = C.conv_pw_dgrad(gy, w)
+        if ctx.needs_input_grad[1]:
+            ws = C.conv_pw_wgrad(gy, x)
+            dw = ws.to(torch.bfloat16).view(w.shape[0], w.shape[1], 1, 1)
+        return dx, dw
+
+
 def stem_buffer_key(x, weight, padding):
     """What a padded stem input buffer is reused by: its shape and device."""
     N, _, H, W = x.shape
@@ -492,10 +561,14 @@ def fda_conv2d(x: torch.Tensor, weight: torch.Tensor, stride=(1, 1),
             and (os.environ.get("FLUXDIST_CONV_DW", _CONV_DW_DEFAULT) != "0"
                  or os.environ.get("FLUXDIST_CONV", "") == "fda")):
         return _FdaConv2dDepthwise.apply(x, weight, stride)
+    if (_native_pw_supported(x, weight, stride, padding, dilation, groups)
+            and (os.environ.get("FLUXDIST_CONV_PW", _CONV_PW_DEFAULT) != "0"
+                 or os.environ.get("FLUXDIST_CONV", "") == "fda")):
+        return _FdaConv2dPointwise.apply(x, weight)
     if os.environ.get("FLUXDIST_CONV", "") == "fda" and x.is_cuda:
         raise RuntimeError(
             f"FLUXDIST_CONV=fda but shape unsupported by conv_igemm, the "
-            f"stem, conv_f32, conv_grouped and conv_dw kernels: "
+            f"stem, conv_f32, conv_grouped, conv_dw and conv_pw kernels: "
             f"x={tuple(x.shape)} w={tuple(weight.shape)} groups={groups}")
     return F.conv2d(x, weight, None, stride, padding, dilation, groups)
 

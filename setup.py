@@ -26,6 +26,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "conv_f32.hip"),
         os.path.join(CSRC, "conv_grouped.hip"),
         os.path.join(CSRC, "conv_dw.hip"),
+        os.path.join(CSRC, "conv_pw.hip"),
         os.path.join(CSRC, "se.hip"),
         os.path.join(CSRC, "preprocess.hip"),
         os.path.join(CSRC, "lars.hip"),

@@ -9,6 +9,7 @@ with effective TFLOP/s. Run on a GPU box:
     python tools/bench_conv.py --dtype fp32   # conv_f32 kernels vs aten fp32
     python tools/bench_conv.py --groups       # conv_grouped vs the library
     python tools/bench_conv.py --depthwise    # conv_dw vs the library
+    python tools/bench_conv.py --pointwise    # conv_pw vs the library
 """
 
 import argparse
@@ -358,6 +359,73 @@ def depthwise_arms(args):
           f"| {tot[2]:8.1f} {tot[3]:8.1f} | {tot[4]:8.1f} {tot[5]:8.1f}")
 
 
+# pointwise convs of MobileNetV1 that conv_pw serves: (C, K, H = W, label)
+PW_SHAPES = [
+    (32, 64, 112, "w1.0"),
+    (8, 16, 112, "w0.25"),
+    (16, 32, 56, "w0.25"),
+    (32, 32, 56, "w0.25"),
+    (32, 64, 28, "w0.25"),
+]
+
+
+def pointwise_arms(args):
+    """Narrow 1x1: the conv_pw kernels against the library's conv on the same
+    tensors, per shape and per leg. us per call: the median of the blocks,
+    and behind each library figure its spread over the blocks,
+    (max - min) / median in percent. min MB: the leg's compulsory traffic (x
+    and y, or dy and dx, or x and dy, once: the same bytes for all three),
+    and after it the rate each native leg reaches on those bytes, in TB/s."""
+    C_ = require_native("conv_pw_fwd")
+    torch.backends.cudnn.benchmark = True
+    n = args.batch
+    print(f"# batch={n} pointwise bf16, us per call: median of {args.repeats} "
+          f"blocks of {args.iters} calls; (..%): spread of the library arm")
+    print(f"{'shape':22s} {'fda_fwd':>8s} {'lib_fwd':>14s} | {'fda_dg':>8s} "
+          f"{'lib_dg':>14s} | {'fda_wg':>8s} {'lib_wg':>14s} | {'min MB':>7s}  "
+          f"fwd/dg/wg TB/s  wgrad (nch, pixels)")
+    shapes = PW_SHAPES if args.only < 0 else [PW_SHAPES[args.only]]
+    cl = torch.channels_last
+    for (c, k, h, label) in shapes:
+        x = torch.randn(n, c, h, h, device="cuda").bfloat16() \
+            .contiguous(memory_format=cl)
+        wt = torch.randn(k, c, 1, 1, device="cuda").bfloat16()
+        gy = torch.randn(n, k, h, h, device="cuda").bfloat16() \
+            .contiguous(memory_format=cl)
+
+        def lib_bwd(mask):
+            return torch.ops.aten.convolution_backward(
+                gy, x, wt, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
+                mask)
+        arms = [
+            lambda: C_.conv_pw_fwd(x, wt),
+            lambda: torch.nn.functional.conv2d(x, wt),
+            lambda: C_.conv_pw_dgrad(gy, wt),
+            lambda: lib_bwd([True, False, False]),
+            lambda: C_.conv_pw_wgrad(gy, x),
+            lambda: lib_bwd([False, True, False]),
+        ]
+        ts = [[] for _ in arms]
+        for _ in range(args.repeats):
+            for i, fn in enumerate(arms):
+                if args.fda_only and i % 2:
+                    ts[i].append(float("nan"))
+                else:
+                    ts[i].append(event_us(fn, args.iters))
+        med = [sorted(t)[len(t) // 2] for t in ts]
+        lib = [f"{med[i]:7.1f} ({100 * (max(ts[i]) - min(ts[i])) / med[i]:2.0f}%)"
+               for i in (1, 3, 5)]
+        nbytes = 2.0 * (x.numel() + gy.numel())
+        rate = [nbytes / med[i] / 1e6 for i in (0, 2, 4)]   # B/us -> TB/s
+        cf = C_.conv_pw_config(n * h * h, c, k, "wgrad")
+        name = f"{c}->{k} {h}x{h} {label}"
+        print(f"{name:22s} {med[0]:8.1f} {lib[0]:>14s} | {med[2]:8.1f} "
+              f"{lib[1]:>14s} | {med[4]:8.1f} {lib[2]:>14s} | "
+              f"{nbytes / 1e6:7.1f}  "
+              f"{rate[0]:.2f}/{rate[1]:.2f}/{rate[2]:.2f}"
+              f"  ({cf[2]}, {cf[3]})", flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, default=96)
@@ -384,8 +452,14 @@ def main():
                    help="the depthwise 3x3 shapes of MobileNetV1: the conv_dw "
                         "kernels against the library, all three legs, with "
                         "the rate reached on the compulsory bytes")
+    p.add_argument("--pointwise", action="store_true",
+                   help="the narrow 1x1 shapes of MobileNetV1 (width 1.0 and "
+                        "0.25): the conv_pw kernels against the library, all "
+                        "three legs, with the library's spread")
     args = p.parse_args()
     assert torch.cuda.is_available()
+    if args.pointwise:
+        return pointwise_arms(args)
     if args.depthwise:
         return depthwise_arms(args)
     if args.groups:
