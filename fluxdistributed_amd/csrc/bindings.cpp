@@ -150,15 +150,19 @@ std::pair<int64_t, int64_t> check_bn_fwd_operands(
     const c10::optional<at::Tensor>& conv_part) {
     auto [rows, C] = nhwc_rows(x);
     const int V = check_vec_channels(op, x, C);
-    TORCH_CHECK((C / V) >= 256 ? (C / V) % 256 == 0 : 256 % (C / V) == 0,
+    // whole 256-lane channel chunks, or one chunk of any C / V lanes (where
+    // 256 % (C / V) != 0 the stats kernels idle the lanes past the last
+    // whole row group)
+    TORCH_CHECK((C / V) < 256 || (C / V) % 256 == 0,
                 "unsupported channel count ", C);
     TORCH_CHECK(weight.scalar_type() == at::kFloat, "BN params must be fp32");
     check_flat(op, "weight", weight, at::kFloat, C);
     check_flat(op, "bias", bias, at::kFloat, C);
     check_flat(op, "running_mean", running_mean, at::kFloat, C);
     check_flat(op, "running_var", running_var, at::kFloat, C);
-    if (training)
-        TORCH_CHECK(C % 64 == 0, "training BN needs C % 64 == 0, got ", C);
+    if (training && conv_part.has_value())
+        TORCH_CHECK(C % 64 == 0, op, ": conv_part needs C % 64 == 0 (no conv "
+                    "produces partials for a narrower layer), got ", C);
     if (training && conv_part.has_value())
         TORCH_CHECK(conv_part->dim() == 3 && conv_part->size(0) >= 1 &&
                         conv_part->size(1) == 2 && conv_part->size(2) == C &&
@@ -282,8 +286,9 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_act_bwd(
     // mask from x (the forward's own expression) and never read `out`.
     const char* op = "bn_act_bwd";
     auto [rows, C] = nhwc_rows(x);
-    dt_of(x);
-    TORCH_CHECK(C % 64 == 0, "BN bwd needs C % 64 == 0, got ", C);
+    const int V = check_vec_channels(op, x, C);
+    TORCH_CHECK((C / V) < 256 || (C / V) % 256 == 0,
+                "unsupported channel count ", C);
     auto gc = gout.contiguous(at::MemoryFormat::ChannelsLast);
     check_like(op, "gout", gc, x, "x");
     check_like(op, "out", out, x, "x");
@@ -1508,6 +1513,125 @@ std::tuple<int64_t, int64_t, int64_t, int64_t> conv_pw_config(
     return {p.nslab, p.pgs, p.gx, p.tpw};
 }
 
+// ---- narrow stem conv (conv_stem_narrow.hip) ---------------------------------
+// Operands: the channels_last bf16 input x [N,Cin,H,W] as stored, the
+// channels_last bf16 weight [K,Cin,3,3] ([K][9*Cin] in memory) and, for the
+// wgrad, channels_last bf16 dy [N,K,P,Q]. Checks in the order of the other
+// conv entry points: dtype, layout, the supported set, sizes, then the device.
+
+void check_stem_narrow_set(const char* op, int64_t Cin, int64_t K,
+                           int64_t stride) {
+    TORCH_CHECK(Cin >= 1 && Cin <= 3, op, ": Cin must be 1, 2 or 3, got ",
+                Cin);
+    TORCH_CHECK(K % 8 == 0 && K >= 8 && K <= 64, op,
+                ": K must be a multiple of 8 in [8, 64], got ", K);
+    TORCH_CHECK(stride == 1 || stride == 2, op,
+                ": stride must be 1 or 2, got ", stride);
+}
+
+void check_stem_narrow_extent(const char* op, int64_t N, int64_t H,
+                              int64_t W) {
+    TORCH_CHECK(N >= 1 && H >= 1 && W >= 1, op,
+                ": needs N, H, W >= 1, got N=", N, " H=", H, " W=", W);
+    TORCH_CHECK(N <= INT32_MAX && H <= INT32_MAX && W <= INT32_MAX &&
+                    N * H <= INT32_MAX && N * H * W <= INT32_MAX,
+                op, ": problem too large (N*H*W must fit int32)");
+}
+
+at::Tensor conv_stem_narrow_fwd(at::Tensor x, at::Tensor w, int64_t stride) {
+    const char* op = "conv_stem_narrow_fwd";
+    check_cl_bf16(op, "x", x);
+    check_cl_bf16(op, "w", w);
+    TORCH_CHECK(w.size(2) == 3 && w.size(3) == 3, op, ": w is [", w.size(0),
+                ", ", w.size(1), ", ", w.size(2), ", ", w.size(3),
+                "] but the narrow stem needs [K, Cin, 3, 3]");
+    const int64_t K = w.size(0), Cin = w.size(1);
+    check_stem_narrow_set(op, Cin, K, stride);
+    TORCH_CHECK(x.size(1) == Cin, op, ": x has ", x.size(1),
+                " channels but w is [", K, ", ", Cin, ", 3, 3]");
+    const int64_t N = x.size(0), H = x.size(2), W = x.size(3);
+    check_stem_narrow_extent(op, N, H, W);
+    const int64_t P = (H - 1) / stride + 1, Q = (W - 1) / stride + 1;
+    check_device(op, {x, w});
+    auto y = at::empty({N, K, P, Q}, x.options().memory_format(
+                                         at::MemoryFormat::ChannelsLast));
+    fda::conv_stem_narrow_launch(x.data_ptr(), w.data_ptr(), y.data_ptr(),
+                                 (int)N, (int)H, (int)W, (int)Cin, (int)K,
+                                 (int)stride, cur_stream());
+    return y;
+}
+
+// dy [N,K,P,Q], x [N,Cin,H,W] -> ws [K][9*Cin] fp32: the channels_last
+// weight's memory order. More than one chunk: slabs and the ordered fold.
+at::Tensor conv_stem_narrow_wgrad(at::Tensor dy, at::Tensor x,
+                                  int64_t stride) {
+    const char* op = "conv_stem_narrow_wgrad";
+    check_cl_bf16(op, "dy", dy);
+    check_cl_bf16(op, "x", x);
+    check_aligned16(op, "dy", dy);
+    const int64_t K = dy.size(1), Cin = x.size(1);
+    check_stem_narrow_set(op, Cin, K, stride);
+    const int64_t N = x.size(0), H = x.size(2), W = x.size(3);
+    check_stem_narrow_extent(op, N, H, W);
+    const int64_t P = (H - 1) / stride + 1, Q = (W - 1) / stride + 1;
+    TORCH_CHECK(dy.size(0) == N && dy.size(2) == P && dy.size(3) == Q, op,
+                ": dy is [", dy.size(0), ", .., ", dy.size(2), ", ",
+                dy.size(3), "] but x [", N, ", .., ", H, ", ", W,
+                "] at stride ", stride, " gives [", N, ", .., ", P, ", ", Q,
+                "]");
+    const auto p = fda::conv_stem_narrow_plan(
+        (int)N, (int)H, (int)W, (int)Cin, (int)K, (int)stride,
+        fda::CONV_STEM_NARROW_WGRAD);
+    const int64_t n = K * 9 * Cin;
+    check_device(op, {dy, x});
+    const auto f32 = x.options().dtype(at::kFloat).memory_format(
+        at::MemoryFormat::Contiguous);
+    auto ws = at::empty({K, 9 * Cin}, f32);
+    auto launch = [&](float* out) {
+        fda::conv_stem_narrow_wgrad_launch(dy.data_ptr(), x.data_ptr(), out,
+                                           (int)N, (int)H, (int)W, (int)Cin,
+                                           (int)K, (int)stride, cur_stream());
+    };
+    if (p.nch == 1) {
+        launch(ws.data_ptr<float>());
+        return ws;
+    }
+    auto slab = at::empty({p.nch * n}, f32);
+    launch(slab.data_ptr<float>());
+    if (p.fold_g == 1) {
+        fda::wgrad_slab_fold_launch(slab.data_ptr<float>(), p.nch, n,
+                                    ws.data_ptr(), false, cur_stream());
+        return ws;
+    }
+    // two levels: sums over j of slab[j*g + i], then over i, each in order
+    auto part = at::empty({p.fold_g * n}, f32);
+    fda::wgrad_slab_fold_launch(slab.data_ptr<float>(), p.nch / p.fold_g,
+                                p.fold_g * n, part.data_ptr(), false,
+                                cur_stream());
+    fda::wgrad_slab_fold_launch(part.data_ptr<float>(), p.fold_g, n,
+                                ws.data_ptr(), false, cur_stream());
+    return ws;
+}
+
+// What the narrow stem kernels run: (th, tw, tiles_h, tiles_w, MFMA tiles or
+// steps per wave, nch, units per chunk, fold groups). fwd: nch == 1 and a
+// block is one (image, tile).
+std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+           int64_t>
+conv_stem_narrow_config(int64_t N, int64_t H, int64_t W, int64_t Cin,
+                        int64_t K, int64_t stride, const std::string& mode) {
+    const char* op = "conv_stem_narrow_config";
+    check_stem_narrow_set(op, Cin, K, stride);
+    check_stem_narrow_extent(op, N, H, W);
+    TORCH_CHECK(mode == "fwd" || mode == "wgrad", op,
+                ": mode must be fwd or wgrad");
+    const auto p = fda::conv_stem_narrow_plan(
+        (int)N, (int)H, (int)W, (int)Cin, (int)K, (int)stride,
+        mode == "fwd" ? fda::CONV_STEM_NARROW_FWD
+                      : fda::CONV_STEM_NARROW_WGRAD);
+    return {p.th, p.tw, p.tiles_h, p.tiles_w, p.upw, p.nch, p.upc, p.fold_g};
+}
+
 // ---- squeeze-and-excitation (se.hip) ---------------------------------------
 // u, identity, out, gout: channels_last bf16 [N,C,H,W]. w1 [Cr,C], b1 [Cr],
 // w2 [C,Cr], b2 [C]: contiguous bf16. s, z [N,C] and h [N,Cr]: fp32.
@@ -2163,6 +2287,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("conv_pw_config", &conv_pw_config,
           "what the pointwise kernels run for M pixels; mode fwd | dgrad | "
           "wgrad (wgrad: elements 2, 3 are nch and pixels per chunk)");
+    m.def("conv_stem_narrow_fwd", &conv_stem_narrow_fwd,
+          "narrow stem conv forward (NHWC bf16, 3x3, padding 1, stride 1 | 2, "
+          "Cin <= 3, K % 8 == 0 in [8, 64]; x and the weight read as stored)");
+    m.def("conv_stem_narrow_wgrad", &conv_stem_narrow_wgrad,
+          "narrow stem conv weight-grad [K][9*Cin] fp32: per-chunk slabs + "
+          "ordered fold, bit-reproducible");
+    m.def("conv_stem_narrow_config", &conv_stem_narrow_config,
+          "(th, tw, tiles_h, tiles_w, MFMA tiles per wave, nch, units per "
+          "chunk, fold groups) the narrow stem kernels run; mode fwd | wgrad");
     m.def("se_fwd", &se_fwd,
           "squeeze-and-excitation tail: (out, s, h, z) = relu(u * s + "
           "identity) with the fp32 gate and its saved intermediates");

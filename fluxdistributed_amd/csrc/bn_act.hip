@@ -18,6 +18,10 @@ namespace fda {
 // Each block writes PARTIAL per-channel sums to part[block][2*chunkC]
 // (plain coalesced stores — a global atomicAdd per channel serializes on
 // L2 and was measured 30x slower); bn_stats_reduce_kernel folds partials.
+// Where 256 % threads-per-row != 0 (24, 40, 48, 96 channels in bf16) the
+// lanes past the last whole row group idle, as in se_reduce_kernel: they run
+// no row (their row would be the next block's first) and block_fold_rows
+// reads the whole groups only.
 template <typename T, int V>
 __global__ void bn_stats_kernel(const T* __restrict__ x,
                                 float* __restrict__ part, int64_t rows, int C,
@@ -35,8 +39,8 @@ __global__ void bn_stats_kernel(const T* __restrict__ x,
 
     // 2 independent row streams per iteration for memory-level parallelism
     const int64_t stride = (int64_t)gridDim.x * rpb;
-    for (int64_t r = (int64_t)blockIdx.x * rpb + sub_r; r < rows;
-         r += 2 * stride) {
+    for (int64_t r = sub_r < rpb ? (int64_t)blockIdx.x * rpb + sub_r : rows;
+         r < rows; r += 2 * stride) {
         T xv[V], xw[V];
         *(uint4*)xv = *(const uint4*)(x + r * C + c0);
         const bool second = r + stride < rows;
@@ -68,7 +72,8 @@ __global__ void bn_stats_kernel(const T* __restrict__ x,
 // chunkC/16, and each thread issues its (up to) FIN_ROWS row loads before
 // the first add. NB <= 512 is one batch; larger NB loops batches. The 64
 // subgroups fold by wave shuffles, then one LDS hop across the 4 waves.
-// chunkC must be a multiple of 16.
+// chunkC is a multiple of 4; where it is no multiple of 16 the last block's
+// channel quads and epilogue threads at or past chunkC do nothing.
 struct BnTotals { float s, q; };
 
 constexpr int FIN_LANES = 4;     // float4 lanes per block -> 16 channels
@@ -91,7 +96,7 @@ __device__ __forceinline__ void bn_reduce_then(const float* __restrict__ part,
         for (int j = 0; j < FIN_ROWS; ++j) {
             const int b = b0 + j * FIN_SUBS;
             a[j] = z[j] = float4{0, 0, 0, 0};
-            if (b < NB) {
+            if (b < NB && cc < chunkC) {
                 const float* p = part + (int64_t)b * 2 * chunkC;
                 a[j] = *(const float4*)(p + cc);
                 z[j] = *(const float4*)(p + chunkC + cc);
@@ -120,7 +125,8 @@ __device__ __forceinline__ void bn_reduce_then(const float* __restrict__ part,
     }
     __syncthreads();
     // one thread per channel: the epilogue's own loads run 16 wide
-    if (threadIdx.x < FIN_CH) {
+    if (threadIdx.x < FIN_CH &&
+        blockIdx.x * FIN_CH + threadIdx.x < chunkC) {
         const int t = threadIdx.x;
         BnTotals tot{sm[0][t] + sm[1][t] + sm[2][t] + sm[3][t],
                      sm[0][FIN_CH + t] + sm[1][FIN_CH + t] +
@@ -269,8 +275,9 @@ __global__ void bn_bwd_stats_kernel(const T* __restrict__ gout,
             sh[k] = bn_shift_of(bias[c0 + k], mu[k], sc[k]);
         }
     }
-    for (int64_t r = (int64_t)blockIdx.x * rpb + sub_r; r < rows;
-         r += (int64_t)gridDim.x * rpb) {
+    // sub_r == rpb: an idle lane past the last whole row group
+    for (int64_t r = sub_r < rpb ? (int64_t)blockIdx.x * rpb + sub_r : rows;
+         r < rows; r += (int64_t)gridDim.x * rpb) {
         T gv[V], xv[V], ov[V];
         *(uint4*)gv = *(const uint4*)(gout + r * C + c0);
         *(uint4*)xv = *(const uint4*)(x + r * C + c0);
@@ -388,7 +395,8 @@ void bn_fwd_finalize_launch(const float* part, int NB, int chunkC, int c_base,
                             float* rv, float* save_mean, float* save_invstd,
                             float* ws, int64_t rows, int C, float momentum,
                             float eps, hipStream_t s) {
-    hipLaunchKernelGGL(bn_fwd_reduce_finalize_kernel, dim3(chunkC / FIN_CH),
+    hipLaunchKernelGGL(bn_fwd_reduce_finalize_kernel,
+                       dim3((chunkC + FIN_CH - 1) / FIN_CH),
                        dim3(256), 0, s, part, weight, bias, rm, rv, save_mean,
                        save_invstd, ws, NB, chunkC, c_base, C, rows, momentum,
                        eps);
@@ -471,7 +479,8 @@ void bn_bwd_stats_launch(const void* gout, const void* x, const void* out,
 void bn_bwd_finalize_launch(const float* part, int NB, int chunkC, int c_base,
                             float* ws, float* gw, float* gb, int64_t rows,
                             int C, bool training, bool accum_g, hipStream_t s) {
-    hipLaunchKernelGGL(bn_bwd_reduce_finalize_kernel, dim3(chunkC / FIN_CH),
+    hipLaunchKernelGGL(bn_bwd_reduce_finalize_kernel,
+                       dim3((chunkC + FIN_CH - 1) / FIN_CH),
                        dim3(256), 0, s, part, ws, gw, gb, NB, chunkC, c_base,
                        C, rows, training ? 1 : 0, accum_g ? 1 : 0);
 }

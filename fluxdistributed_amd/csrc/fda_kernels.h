@@ -405,6 +405,35 @@ void conv_pw_launch(const void* src, const void* w, void* out, long M, int C,
 void conv_pw_wgrad_launch(const void* dy, const void* x, float* ws, long M,
                           int C, int K, hipStream_t stream);
 
+// Narrow stem conv, NHWC bf16 (conv_stem_narrow.hip): 3x3, padding 1, stride
+// 1 or 2, Cin in {1, 2, 3}, K % 8 == 0 in [8, 64]; forward and wgrad, no
+// dgrad. x is read as stored, the weight is w [K][9*Cin] as stored
+// (channels_last [K,Cin,3,3]).
+// What a launch runs: th x tw output tiles, tiles_h x tiles_w of them per
+// image, tw a multiple of the MFMA width (16 pixels forward, 32 wgrad).
+// fwd: one block per (image, tile), a wave walks upw 16-pixel MFMA tiles.
+// wgrad: the (image, tile) units go in nch chunks of upc, one block each; a
+// wave runs upw 32-pixel MFMA steps per unit; fold_g as in ConvPwPlan.
+constexpr int CONV_STEM_NARROW_FWD = 0;
+constexpr int CONV_STEM_NARROW_WGRAD = 1;
+struct ConvStemNarrowPlan {
+    int th, tw, tiles_h, tiles_w, upw;
+    int nch, upc, fold_g;   // wgrad
+    long blocks;
+};
+ConvStemNarrowPlan conv_stem_narrow_plan(int N, int H, int W, int Cin, int K,
+                                         int stride, int mode);
+// x [N,H,W,Cin], w [K][9*Cin] -> y [N,P,Q,K], P = (H-1)/stride + 1
+void conv_stem_narrow_launch(const void* x, const void* w, void* y, int N,
+                             int H, int W, int Cin, int K, int stride,
+                             hipStream_t stream);
+// plan.nch == 1: ws is the result [K][9*Cin] fp32. nch > 1: ws is
+// [nch][K][9*Cin], chunk c stores into slab c (the chunks past the last unit
+// store zeros) and wgrad_slab_fold_launch sums them as for conv_pw.
+void conv_stem_narrow_wgrad_launch(const void* dy, const void* x, float* ws,
+                                   int N, int H, int W, int Cin, int K,
+                                   int stride, hipStream_t stream);
+
 // Squeeze-and-Excitation block tail (se.hip), NHWC bf16 activations:
 //   out = relu(u * s[n][c] + identity), s = sigmoid(W2 relu(W1 mean_hw(u) +
 //   b1) + b2). C % 64 == 0, 64 <= C <= 2048; Cr % 4 == 0, 4 <= Cr <= 128.

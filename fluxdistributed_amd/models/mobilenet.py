@@ -8,14 +8,21 @@ On the GPU the depthwise convs run on csrc/conv_dw.hip (FLUXDIST_CONV_DW),
 the pointwise convs on conv_igemm where both channel counts are multiples of
 64 and, with FLUXDIST_CONV_PW=1, on csrc/conv_pw.hip where they are narrower
 (the first one at width 1.0, most of them at smaller widths, up to 256
-channels); BN+ReLU is the fused op. At width 1.0 the stem (K = 32) is outside
-every native conv path and stays on the library; so do the two 32-channel BNs
-(after the stem and after the first depthwise conv), because the fused BN
-kernels train multiples of 64 channels only (BNAct below).
+channels); BN+ReLU is the fused op. The stem (K = 32 at width 1.0, 8 to 24 at
+smaller widths) runs on csrc/conv_stem_narrow.hip with
+FLUXDIST_CONV_STEM_NARROW=1 (opt-in: its wgrad is slower than the library's
+at 224x224) and stays on the library otherwise. The BNs whose channel count
+is a multiple of 8 but not of 64 (the two 32-channel ones at width 1.0, after
+the stem and after the first depthwise conv; more at smaller widths) run on
+the fused BN kernels too (FLUXDIST_BN_NARROW, on by default; BNAct below).
+With FLUXDIST_CONV_STEM_NARROW=1 and FLUXDIST_CONV_PW=1, or with
+FLUXDIST_CONV=fda, no conv or BN of a training step at widths 0.25 to 1.0
+goes to the library. Defaults and their measured reasons: docs/kernels.md.
 
 Conv weights are bias-free, like the ResNets'.
 """
 
+import os
 from typing import List, Tuple
 
 import torch
@@ -38,15 +45,27 @@ def _width(channels: int, mult: float) -> int:
     return max(8, int(channels * mult + 4) // 8 * 8)
 
 
+# On by default: at 32 channels and 96x112x112 the native pair is 4.4x (fwd)
+# and 4.5x (bwd) faster than the composition, the step 1.16x
+# (profiles/conv_stem_narrow.md).
+_BN_NARROW_DEFAULT = "1"
+
+
 class BNAct(FusedBNAct):
-    """FusedBNAct for any channel count. The native BN kernels train
-    C % 64 == 0 only; a narrower layer on the GPU (32 channels at width 1.0,
-    other widths at other multipliers) is the composition of library ops
-    that batch_norm_act uses as its CPU form, in fp32. Same parameters,
-    buffers and state dict either way."""
+    """FusedBNAct for any channel count. Multiples of 64 channels always run
+    the native BN kernels. A narrower layer on the GPU (32 channels at width
+    1.0, other widths at other multipliers) runs them too where the count is
+    a multiple of 8, in bf16, unless FLUXDIST_BN_NARROW=0 (read at call time);
+    with FLUXDIST_BN_NARROW=0 and for other counts it is the composition of
+    library ops that batch_norm_act uses as its CPU form, in fp32. Same
+    parameters, buffers and state dict either way."""
 
     def forward(self, x):
-        if self.num_features % 64 == 0 or not x.is_cuda:
+        C = self.num_features
+        if C % 64 == 0 or not x.is_cuda or (
+                C % 8 == 0 and x.dtype == torch.bfloat16
+                and os.environ.get("FLUXDIST_BN_NARROW",
+                                   _BN_NARROW_DEFAULT) != "0"):
             return super().forward(x)
         if self.training:
             self._nbt_pending += 1

@@ -6,9 +6,24 @@ MI355X-native path is fluxdistributed_amd/csrc/conv_igemm.hip —
 v_mfma_f32_16x16x32_bf16 tiles, LDS-staged via global_load_lds. Supported
 there: NHWC bf16, dilation 1, groups 1, C and K multiples of 64 (all
 ResNet body convs) — fwd, dgrad AND wgrad. Small-C stems (C<=5, e.g. the
-ImageNet 7x7 and CIFAR 3x3 stems) run on the dedicated CONV_STEM kernels;
-only genuinely unsupported shapes (dilated, odd channel counts, grouped
-convs outside the set below) fall back to the library path.
+ImageNet 7x7 and CIFAR 3x3 stems) run on the dedicated CONV_STEM kernels
+where K is a multiple of 64; only genuinely unsupported shapes (dilated, odd
+channel counts, grouped convs outside the set below) fall back to the
+library path.
+
+Narrow stems (3x3, padding 1, stride 1 or 2, Cin <= 3, K a multiple of 8 in
+[8, 64] that the CONV_STEM kernels do not take: the MobileNetV1 stem, K = 8
+to 32) have csrc/conv_stem_narrow.hip: bf16, x read as stored (no padded
+copy, no buffer pool), the whole reduction of 9*Cin values in one MFMA K-step,
+the weight [K][3][3][Cin] read as stored and held in registers, wgrad through
+per-chunk slabs and the ordered fold. Forward and wgrad only: like the
+CONV_STEM kernels it has no dgrad, and an input that requires grad goes to
+the library. Plain autograd. The path is opt-in
+(FLUXDIST_CONV_STEM_NARROW=1): against the library its forward is faster on
+all five measured MobileNetV1 stems (44 vs 58 us for 3 -> 32 at 224x224) but
+its wgrad is slower on the four 224x224 ones (78 vs 60 us) and the step does
+not gain (profiles/conv_stem_narrow.md), so by the rule that defaults are
+measured winners the default is 0.
 
 Grouped 3x3 convs (the ResNeXt bottlenecks) have kernels of their own,
 csrc/conv_grouped.hip: bf16, padding 1, stride 1 or 2, C/g == K/g in
@@ -68,6 +83,10 @@ Env:
                          library (0, the default). Read at call time.
                          FLUXDIST_CONV=miopen overrides it, FLUXDIST_CONV=fda
                          implies 1.
+  FLUXDIST_CONV_STEM_NARROW=1|0  narrow stem convs on conv_stem_narrow.hip
+                         (1) or the library (0, the default). Read at call
+                         time. FLUXDIST_CONV=miopen overrides it,
+                         FLUXDIST_CONV=fda implies it.
   FLUXDIST_WGRAD_SLAB=0  weight-grads into flat G: atomic workspace + queued
                          flush for every shape (default 1: slabs + ordered
                          fold where conv_igemm_wgrad_mode says "slab")
@@ -539,6 +558,69 @@ def _stem_supported(x, weight, stride, padding, dilation, groups) -> bool:
     return Cin <= 5 and S <= 7 and K % 64 == 0 and load_native() is not None
 
 
+_CONV_STEM_NARROW_DEFAULT = "0"
+
+
+def _native_stem_narrow_supported(x: torch.Tensor, w: torch.Tensor, stride,
+                                  padding, dilation, groups) -> bool:
+    """Stem convs the conv_stem_narrow kernels serve, FLUXDIST_CONV_STEM_NARROW
+    aside: bf16, 3x3, padding 1, stride 1 or 2, groups 1, Cin <= 3, K a
+    multiple of 8 in [8, 64], and an input that needs no gradient (there is
+    no dgrad, as in the CONV_STEM kernels)."""
+    if os.environ.get("FLUXDIST_CONV", "") == "miopen":
+        return False
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16):
+        return False
+    if groups != 1 or _pair(dilation) != (1, 1) or _pair(padding) != (1, 1):
+        return False
+    if _pair(stride) not in ((1, 1), (2, 2)) or tuple(w.shape[2:]) != (3, 3):
+        return False
+    if x.requires_grad and torch.is_grad_enabled():
+        return False
+    K, Cin = w.shape[0], w.shape[1]
+    if Cin > 3 or K % 8 != 0 or not 8 <= K <= 64:
+        return False
+    return load_native() is not None
+
+
+class _FdaStemConv2dNarrow(torch.autograd.Function):
+    """Narrow stem forward and weight-grad on the conv_stem_narrow kernels.
+    Both read x as stored (no padded copy, no pool: x itself is saved, so a
+    second backward works) and the weight as stored ([K][3][3][Cin],
+    channels_last); the weight-grad comes back fp32 in that memory order and
+    is cast once. No dgrad (the stem input is data). Plain autograd: no
+    conv->BN stats, no arenas, no direct write into flat G."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride):
+        C = require_native("conv_stem_narrow_fwd")
+        clear_conv_stats()
+        xc = x.contiguous(memory_format=torch.channels_last)
+        wc = weight.contiguous(memory_format=torch.channels_last)
+        y = C.conv_stem_narrow_fwd(xc, wc, stride[0])
+        ctx.save_for_backward(xc)
+        ctx.conf = (stride[0], tuple(weight.shape))
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        if ctx.needs_input_grad[0]:
+            raise RuntimeError(
+                "conv_stem_narrow has no input-grad path (stem inputs are "
+                "data); fda_conv2d should have routed this conv to the "
+                "library — x.requires_grad was set after dispatch?")
+        (x,) = ctx.saved_tensors
+        stride, (K, Cin, _, _) = ctx.conf
+        dw = None
+        if ctx.needs_input_grad[1]:
+            C = require_native("conv_stem_narrow_wgrad")
+            gyc = gy.contiguous(memory_format=torch.channels_last)
+            ws = C.conv_stem_narrow_wgrad(gyc, x, stride)
+            dw = (ws.to(torch.bfloat16).view(K, 3, 3, Cin)
+                  .permute(0, 3, 1, 2))
+        return None, dw, None
+
+
 def fda_conv2d(x: torch.Tensor, weight: torch.Tensor, stride=(1, 1),
                padding=(0, 0), dilation=(1, 1), groups: int = 1) -> torch.Tensor:
     """conv2d with per-shape dispatch to the native MFMA kernel."""
@@ -548,6 +630,12 @@ def fda_conv2d(x: torch.Tensor, weight: torch.Tensor, stride=(1, 1),
     if _stem_supported(x, weight, stride, padding, dilation, groups):
         return _FdaStemConv2d.apply(x, weight, stride, padding,
                                     _want_conv_stats())
+    if (_native_stem_narrow_supported(x, weight, stride, padding, dilation,
+                                      groups)
+            and (os.environ.get("FLUXDIST_CONV_STEM_NARROW",
+                                _CONV_STEM_NARROW_DEFAULT) != "0"
+                 or os.environ.get("FLUXDIST_CONV", "") == "fda")):
+        return _FdaStemConv2dNarrow.apply(x, weight, stride)
     if (_native_f32_supported(x, weight, stride, padding, dilation, groups)
             and (os.environ.get("FLUXDIST_CONV_F32", _CONV_F32_DEFAULT) != "0"
                  or os.environ.get("FLUXDIST_CONV", "") == "fda")):
@@ -568,7 +656,8 @@ def fda_conv2d(x: torch.Tensor, weight: torch.Tensor, stride=(1, 1),
     if os.environ.get("FLUXDIST_CONV", "") == "fda" and x.is_cuda:
         raise RuntimeError(
             f"FLUXDIST_CONV=fda but shape unsupported by conv_igemm, the "
-            f"stem, conv_f32, conv_grouped, conv_dw and conv_pw kernels: "
+            f"stem, conv_stem_narrow, conv_f32, conv_grouped, conv_dw and "
+            f"conv_pw kernels: "
             f"x={tuple(x.shape)} w={tuple(weight.shape)} groups={groups}")
     return F.conv2d(x, weight, None, stride, padding, dilation, groups)
 

@@ -27,6 +27,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "conv_grouped.hip"),
         os.path.join(CSRC, "conv_dw.hip"),
         os.path.join(CSRC, "conv_pw.hip"),
+        os.path.join(CSRC, "conv_stem_narrow.hip"),
         os.path.join(CSRC, "se.hip"),
         os.path.join(CSRC, "preprocess.hip"),
         os.path.join(CSRC, "lars.hip"),

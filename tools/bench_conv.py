@@ -10,6 +10,7 @@ with effective TFLOP/s. Run on a GPU box:
     python tools/bench_conv.py --groups       # conv_grouped vs the library
     python tools/bench_conv.py --depthwise    # conv_dw vs the library
     python tools/bench_conv.py --pointwise    # conv_pw vs the library
+    python tools/bench_conv.py --stem-narrow  # conv_stem_narrow, narrow BN
 """
 
 import argparse
@@ -426,6 +427,110 @@ def pointwise_arms(args):
               f"  ({cf[2]}, {cf[3]})", flush=True)
 
 
+# narrow stems of MobileNetV1: (K, H = W, stride, label)
+STEM_NARROW_SHAPES = [
+    (8, 224, 2, "w0.25"),
+    (16, 224, 2, "w0.5"),
+    (24, 224, 2, "w0.75"),
+    (32, 224, 2, "w1.0"),
+    (32, 32, 1, "w1.0 small_input"),
+]
+
+
+def _blocks(arms, args):
+    """event_us of every arm, args.repeats blocks, the arms alternating."""
+    ts = [[] for _ in arms]
+    for _ in range(args.repeats):
+        for i, fn in enumerate(arms):
+            if args.fda_only and i % 2:
+                ts[i].append(float("nan"))
+            else:
+                ts[i].append(event_us(fn, args.iters))
+    med = [sorted(t)[len(t) // 2] for t in ts]
+    lib = [f"{med[i]:7.1f} ({100 * (max(ts[i]) - min(ts[i])) / med[i]:2.0f}%)"
+           for i in range(1, len(arms), 2)]
+    return med, lib
+
+
+def stem_narrow_arms(args):
+    """The conv_stem_narrow kernels against the library's conv on the same
+    tensors (forward and weight-grad; there is no dgrad), then the narrow
+    BatchNorm: the native bn_act_fwd / bn_act_bwd pair on 32 channels at
+    112x112 against the fp32 library composition BNAct falls back to (its
+    backward through autograd). us per call: the median of the blocks, the
+    arms alternating; behind each library figure its spread over the blocks,
+    (max - min) / median in percent. min MB and TB/s as for --pointwise."""
+    C_ = require_native("conv_stem_narrow_fwd")
+    F = torch.nn.functional
+    torch.backends.cudnn.benchmark = True
+    n = args.batch
+    cl = torch.channels_last
+    print(f"# batch={n} narrow stem bf16, us per call: median of "
+          f"{args.repeats} blocks of {args.iters} calls; (..%): spread of the "
+          f"library arm")
+    print(f"{'shape':28s} {'fda_fwd':>8s} {'lib_fwd':>14s} | {'fda_wg':>8s} "
+          f"{'lib_wg':>14s} | {'min MB':>7s}  fwd/wg TB/s  wgrad (nch, upc)")
+    shapes = (STEM_NARROW_SHAPES if args.only < 0
+              else [STEM_NARROW_SHAPES[args.only]])
+    for (k, h, s, label) in shapes:
+        x = torch.randn(n, 3, h, h, device="cuda").bfloat16() \
+            .contiguous(memory_format=cl)
+        wt = torch.randn(k, 3, 3, 3, device="cuda").bfloat16() \
+            .contiguous(memory_format=cl)
+        q = (h - 1) // s + 1
+        gy = torch.randn(n, k, q, q, device="cuda").bfloat16() \
+            .contiguous(memory_format=cl)
+        arms = [
+            lambda: C_.conv_stem_narrow_fwd(x, wt, s),
+            lambda: F.conv2d(x, wt, None, s, 1),
+            lambda: C_.conv_stem_narrow_wgrad(gy, x, s),
+            lambda: torch.ops.aten.convolution_backward(
+                gy, x, wt, None, [s, s], [1, 1], [1, 1], False, [0, 0], 1,
+                [False, True, False]),
+        ]
+        med, lib = _blocks(arms, args)
+        nbytes = 2.0 * (x.numel() + gy.numel())
+        cf = C_.conv_stem_narrow_config(n, h, h, 3, k, s, "wgrad")
+        name = f"3->{k} {h}x{h}/{s} {label}"
+        print(f"{name:28s} {med[0]:8.1f} {lib[0]:>14s} | {med[2]:8.1f} "
+              f"{lib[1]:>14s} | {nbytes / 1e6:7.1f}  "
+              f"{nbytes / med[0] / 1e6:.2f}/{nbytes / med[2] / 1e6:.2f}"
+              f"  ({cf[5]}, {cf[6]})", flush=True)
+
+    c, h = 32, 112
+    x = torch.randn(n, c, h, h, device="cuda").bfloat16() \
+        .contiguous(memory_format=cl)
+    gy = torch.randn_like(x)
+    w = torch.rand(c, device="cuda") + 0.5
+    b = torch.randn(c, device="cuda")
+    rm, rv = torch.zeros(c, device="cuda"), torch.ones(c, device="cuda")
+    none = torch.empty(0, device="cuda", dtype=torch.bfloat16)
+    out, mean, invstd = C_.bn_act_fwd(x, w, b, rm, rv, True, 0.1, 1e-5, True,
+                                      none)
+
+    def lib_fwd():
+        o = F.batch_norm(x.float(), rm, rv, w, b, True, 0.1, 1e-5)
+        return torch.relu(o).to(x.dtype)
+
+    xr = x.detach().requires_grad_(True)
+    wr, br = w.detach().requires_grad_(True), b.detach().requires_grad_(True)
+    yr = torch.relu(F.batch_norm(xr.float(), rm, rv, wr, br, True, 0.1,
+                                 1e-5)).to(x.dtype)
+    arms = [
+        lambda: C_.bn_act_fwd(x, w, b, rm, rv, True, 0.1, 1e-5, True, none),
+        lib_fwd,
+        lambda: C_.bn_act_bwd(gy, x, w, mean, invstd, out, True, True, None,
+                              None, False, b),
+        lambda: torch.autograd.grad(yr, (xr, wr, br), gy, retain_graph=True),
+    ]
+    med, lib = _blocks(arms, args)
+    print(f"# BN+ReLU training, {c} channels, {n}x{h}x{h} bf16")
+    print(f"{'':28s} {'fda_fwd':>8s} {'lib_fwd':>14s} | {'fda_bwd':>8s} "
+          f"{'lib_bwd':>14s}")
+    print(f"{'bn_act ' + str(c):28s} {med[0]:8.1f} {lib[0]:>14s} | "
+          f"{med[2]:8.1f} {lib[1]:>14s}", flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, default=96)
@@ -456,8 +561,15 @@ def main():
                    help="the narrow 1x1 shapes of MobileNetV1 (width 1.0 and "
                         "0.25): the conv_pw kernels against the library, all "
                         "three legs, with the library's spread")
+    p.add_argument("--stem-narrow", action="store_true",
+                   help="the MobileNetV1 stems (K = 8 .. 32): the "
+                        "conv_stem_narrow kernels against the library, forward "
+                        "and weight-grad, then the 32-channel training BN "
+                        "against the library composition")
     args = p.parse_args()
     assert torch.cuda.is_available()
+    if args.stem_narrow:
+        return stem_narrow_arms(args)
     if args.pointwise:
         return pointwise_arms(args)
     if args.depthwise:
